@@ -19,9 +19,17 @@ rectification workloads consecutive fused launches alternate between two HIP
 streams, so one launch's workgroups take the CUs the other's early finishers
 free -- GCR_VERIFY_OVERLAP=0 keeps them on one stream) and bracketed by device
 synchronisation.  Features are uploaded once before
-timing (HBM-resident).  `value` is the whole-job hypotheses/s; the end-to-end
-latency of a full estimator call at confidence 0.99 (including LO and the
-final refit) is reported beside it.
+timing (HBM-resident).  `value` is the whole-job hypotheses/s.
+
+A plain run sets up, warms up, times the K steps and prints the line.  `--full`
+adds what the headline figure does not need: the CPU baseline legs, the
+end-to-end latency of a full estimator call at confidence 0.99 (including LO
+and the final refit), the HBM copy probe and the VALU roofline from the
+committed PMC passes; without it those fields of the line are null.
+`--dump-outputs DIR` writes the record the last timed step returned (models,
+iterations, best_slot, best_score, best_inliers, best_model) as
+DIR/<name>.npy, float64; the inputs are seeded, so two builds run with the
+same arguments can be compared file by file.
 
 Multi-GPU: one process per GPU.  `--gpus N` without a launcher's WORLD_SIZE
 spawns the N ranks itself (fresh child processes with RANK / LOCAL_RANK /
@@ -269,6 +277,12 @@ def parse(argv=None):
     ap.add_argument("--cpu-seconds", type=float, default=10.0, help="CPU baseline budget per leg (0 = skip)")
     ap.add_argument("--no-latency", action="store_true")
     ap.add_argument("--no-hbm-probe", action="store_true", help="skip the measured-HBM-peak copy probe")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the CPU baseline legs, the wall time "
+                         "to 0.99 confidence (full estimator calls), the HBM copy probe and the PMC-based VALU "
+                         "roofline (--cpu-seconds, --no-latency and --no-hbm-probe trim these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float64)")
     return ap.parse_args(argv)
 
 
@@ -318,6 +332,26 @@ def launch_ranks(argv, world, script=None):
         except subprocess.TimeoutExpired:
             p.kill()
     return rc
+
+
+def last_step_outputs(rec):
+    """The arrays a caller of the timed path receives for one step (one
+    gcr_batch_result record of gcr_problem_verify_batches), as float64: every
+    integer field is far below 2^53."""
+    import numpy as np
+
+    return {k: np.asarray(rec[k], dtype=np.float64).reshape(-1)
+            for k in ("models", "iterations", "best_slot", "best_score", "best_inliers", "best_model")}
+
+
+def dump_outputs(outdir, rank, arrays):
+    """--dump-outputs: rank 0 writes DIR/<name>.npy, rank r > 0 DIR/<name>.rank<r>.npy"""
+    import numpy as np
+
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, f"{name}.npy" if rank == 0 else f"{name}.rank{rank}.npy"),
+                np.ascontiguousarray(a, dtype=np.float64))
 
 
 def workload_problem(name, seed):
@@ -444,7 +478,8 @@ def main():
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     cpu = None
-    if rank == 0 and world == 1 and args.cpu_seconds > 0 and args.workload != "batch" and args.mode == "weak":
+    if (args.full and rank == 0 and world == 1 and args.cpu_seconds > 0 and args.workload != "batch"
+            and args.mode == "weak"):
         cpu = cpu_baseline(args)               # host cores only, before the GPU is touched
     # "nccl" is RCCL on ROCm; GCR_DIST_BACKEND=gloo rehearses the multi-rank
     # path on fewer GPUs than ranks (host tensors, ranks share devices)
@@ -546,6 +581,8 @@ def main():
     barrier()
     elapsed = time.perf_counter() - t0
     account(*timed, args.steps, acc)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, last_step_outputs(np.frombuffer(timed[0], dtype=rec_dt)[-1]))
 
     models_total = acc["models"]
     gathered = 1
@@ -590,7 +627,7 @@ def main():
     # cycles spent issuing VALU during one launch -- the bound the algorithmic
     # HBM figure above does not see (the features are L2-resident)
     build_id = N.lib.gcr_kernel_build_id().decode()
-    pmc = pmc_entry(kernel_name, args.slots, build_id)
+    pmc = pmc_entry(kernel_name, args.slots, build_id) if args.full else None
     if pmc and "SQ_ACTIVE_INST_VALU" in pmc and avg_kernel_s > 0:
         simd_cycles = N_SIMD * avg_kernel_s * CLOCK_GHZ * 1e9
         valu = dict(valu or {})
@@ -625,7 +662,7 @@ def main():
 
     # wall time to 0.99 confidence: full estimator call (incl. upload, LO, refit)
     latency = None
-    if not args.no_latency and rank == 0:
+    if args.full and not args.no_latency and rank == 0:
         lat, stats_all = [], []
         # r = -1: one untimed warm-up call (seed 99: the first call of a
         # process allocates the context's pinned LO / refit buffers, ~2 ms)
@@ -664,7 +701,7 @@ def main():
 
     # the box's achievable HBM bandwidth (streaming copy), beside the spec peak
     hbm_meas = None
-    if rank == 0 and not args.no_hbm_probe:
+    if args.full and rank == 0 and not args.no_hbm_probe:
         g = C.c_double(0.0)
         if N.lib.gcr_measure_hbm(ctx, 2 << 30, 10, C.byref(g)) == 0 and g.value > 0:
             hbm_meas = g.value
@@ -682,6 +719,7 @@ def main():
             "scaling": "weak",
             "vs_baseline": None,
             "dtype": "f64",
+            "full": args.full,
             "data": "synthetic (seeded M2/M1 generator, pygcransac/synthetic.py; notebook features absent)",
             "config": {
                 "workload": workload,
@@ -795,9 +833,15 @@ def bench_strong(args, rank, world, dist, device, coll_dev, backend):
         run(budget)                                       # -- pinned buffers included -- is reused)
     barrier()
     t0 = time.perf_counter()
-    _, masks, st, _ = run(budget)
+    H, masks, st, _ = run(budget)
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        import numpy as np
+
+        out = {"H": np.zeros(9) if H is None else np.asarray(H).reshape(-1)}
+        out.update({f"mask{i}": m for i, m in enumerate(masks)})
+        dump_outputs(args.dump_outputs, rank, out)
     if dist is not None:
         import torch
 
@@ -903,6 +947,14 @@ def bench_batch(args, rank, world, dist, device, coll_dev):
     barrier()
     elapsed = time.perf_counter() - t0
     hyps = float(sum(r["hypotheses"] for r in recs if r is not None))
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+
+        # every rank holds the gathered records of all problems: num_inliers, H, model, iterations, hypotheses
+        rows = [np.zeros(19) if r is None else
+                np.concatenate([[r["num_inliers"]], np.zeros(9) if r["H"] is None else r["H"].reshape(-1),
+                                list(r["model"].values()), [r["iteration_number"], r["hypotheses"]]]) for r in recs]
+        dump_outputs(args.dump_outputs, 0, {"records": np.array(rows).reshape(len(recs), 19)})
     if dist is not None:
         import torch
 

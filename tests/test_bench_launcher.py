@@ -58,6 +58,33 @@ def test_launcher_propagates_a_failing_rank(tmp_path):
     assert out.returncode == 3
 
 
+def test_plain_run_is_the_default_and_full_is_an_option():
+    plain = bench.parse(["--gpus", "1", "--steps", "7", "--warmup", "2"])
+    assert plain.full is False and plain.dump_outputs is None and plain.steps == 7 and plain.warmup == 2
+    full = bench.parse(["--full", "--dump-outputs", "out"])
+    assert full.full is True and full.dump_outputs == "out"
+
+
+def test_dump_outputs_writes_float64_npy_per_name(tmp_path):
+    import numpy as np
+
+    rec = np.zeros(1, dtype=[("models", "<u8"), ("iterations", "<u8"), ("best_slot", "<i8"), ("best_score", "<f8"),
+                             ("best_inliers", "<u8", 2), ("best_model", "<f8", 7)])[0]
+    rec["models"], rec["best_slot"], rec["best_score"] = 4001, -1, 0.1
+    rec["best_inliers"], rec["best_model"] = (3, 5), np.arange(7) / 3.0
+    arrays = bench.last_step_outputs(rec)
+    bench.dump_outputs(str(tmp_path / "d"), 0, arrays)
+    bench.dump_outputs(str(tmp_path / "d"), 1, {"models": arrays["models"]})
+    names = sorted(os.listdir(tmp_path / "d"))
+    assert names == ["best_inliers.npy", "best_model.npy", "best_score.npy", "best_slot.npy", "iterations.npy",
+                     "models.npy", "models.rank1.npy"]
+    got = {n: np.load(tmp_path / "d" / n) for n in names}
+    assert all(a.dtype == np.float64 and a.ndim == 1 for a in got.values())
+    assert got["models.npy"].tolist() == [4001.0] and got["best_slot.npy"].tolist() == [-1.0]
+    assert got["best_inliers.npy"].tolist() == [3.0, 5.0]
+    assert np.array_equal(got["best_model.npy"], np.arange(7) / 3.0) and got["best_score.npy"].tolist() == [0.1]
+
+
 def test_parent_does_not_load_the_engine_before_spawning():
     # the launcher path returns before `pygcransac._native` is imported
     src = open(os.path.join(REPO, "bench.py")).read()

@@ -20,6 +20,10 @@ MSAC_scoring_function.hpp:108-127).  Full-size problems (M2 5000 + 5000, M1
 consecutive batches from an unaligned slot.
 """
 import ctypes as C
+import json
+import os
+import subprocess
+import sys
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
@@ -32,6 +36,7 @@ from pygcransac import synthetic as S
 
 pytestmark = pytest.mark.gpu
 
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SEED = 20251121          # bench.py's problem and sampler seed (rank 0)
 NB = 3
 SLOT0 = 7
@@ -150,6 +155,44 @@ def test_correspondence_verify_matches_oracle_replay_at_bench_config(solver, nsl
         assert r.best_slot == bslot and bslot >= 0, (b, r.best_slot, bslot)
         assert bits(r.best_score) == bits(best), b
         assert r.best_inliers[0] == bcnt, b
+
+
+def test_plain_bench_run_dumps_its_last_timed_step(tmp_path):
+    # `bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR`: a plain run
+    # (no --full) leaves the extra legs out of the line, times exactly K
+    # steps, and writes the record of its last timed step -- batch W + K - 1
+    # of the M2 problem -- which must equal the same batch verified here
+    steps, warmup, slots = 3, 2, 4096
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", str(steps),
+                          "--warmup", str(warmup), "--dump-outputs", str(tmp_path / "dump")],
+                         capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    line = json.loads(out.stdout.strip().splitlines()[-1])
+    assert line["steps"] == steps and line["warmup"] == warmup and line["full"] is False
+    assert line["unit"] == "hypotheses/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["ms_per_step"] > 0.0
+    # value = scored hypotheses of the K steps / their time
+    assert line["value"] == pytest.approx(line["roofline"]["hypotheses_per_launch"] / (line["ms_per_step"] * 1e-3))
+    assert line["cpu_baseline"] is None and line["wall_time_to_0.99_confidence"] is None
+    assert line["roofline"]["algorithmic_hbm"]["measured_peak_gbs"] is None
+    got = {f[:-4]: np.load(tmp_path / "dump" / f) for f in sorted(os.listdir(tmp_path / "dump"))}
+    assert sorted(got) == ["best_inliers", "best_model", "best_score", "best_slot", "iterations", "models"]
+    assert all(a.dtype == np.float64 for a in got.values())
+
+    fs, fo, ts, to = _rect_problem(N.SOLVER_SIFT22)
+    prob = Problem(N.SOLVER_SIFT22, fs, fo)
+    p = N.default_params()
+    p.scale_residual_thresh, p.orientation_residual_thresh, p.seed = ts, to, SEED
+    res = (N.BatchResult * 1)()
+    N.check(N.lib.gcr_problem_verify_batches(prob.h, C.byref(p), (warmup + steps - 1) * slots, slots, 1, res, None))
+    r = res[0]
+    assert r.best_slot >= 0
+    assert got["models"].tolist() == [r.models] and got["iterations"].tolist() == [r.iterations]
+    assert got["best_slot"].tolist() == [r.best_slot]
+    assert bits(got["best_score"]).tolist() == [bits(r.best_score).item()]
+    assert got["best_inliers"].tolist() == [r.best_inliers[0], r.best_inliers[1]]
+    m = r.best_model
+    assert np.array_equal(bits(got["best_model"]), bits([m.x0, m.y0, m.s, m.h7, m.h8, m.alpha, m.phi]))
 
 
 @pytest.mark.parametrize("solver", [N.SOLVER_HOMOGRAPHY4, N.SOLVER_FUNDAMENTAL7])

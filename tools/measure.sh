@@ -18,10 +18,10 @@ step smoke
 timeout -k 10 300 python -u -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke.log 2>&1 || { tail -20 $O/smoke.log; exit 1; }
 tail -1 $O/smoke.log
 step bench
-timeout -k 10 600 python -u bench.py > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full > $O/bench.log 2>&1 || { tail -20 $O/bench.log; exit 1; }
 tail -1 $O/bench.log > $O/bench.json
 step bench_f
-timeout -k 10 600 python -u bench.py --workload f --steps 200 --warmup 20 --cpu-seconds 0 > $O/bench_f.log 2>&1 || { tail -20 $O/bench_f.log; exit 1; }
+timeout -k 10 600 python -u bench.py --full --workload f --steps 200 --warmup 20 --cpu-seconds 0 > $O/bench_f.log 2>&1 || { tail -20 $O/bench_f.log; exit 1; }
 tail -1 $O/bench_f.log > $O/bench_f.json
 fi
 [ "$PART" = "run" ] && exit 0
