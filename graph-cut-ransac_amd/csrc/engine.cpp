@@ -52,6 +52,7 @@
 #include "gcr.h"
 #include "host_fit.h"
 #include "kernels.h"
+#include "fm_groups.h"
 #include "philox.h"
 #include "qr3.h"
 #include "graphcut.h"
@@ -1355,16 +1356,14 @@ struct RectTraits {
     }
     // batch b of nb: chained launches (the previous launch generated this
     // batch's slots, this one generates the next batch's) when the kernel
-    // at this batch size supports it (verify_chains)
-    // ahead = 2 (verify_batches' two-stream overlap): batches alternate
-    // between two streams, batch b chains to b + 2 (same stream) and uses
-    // buffer set b & 1 for its per-slot outputs; its ring selection is left
-    // to the caller (select_flush), which orders it after both streams
+    // at this batch size supports it (verify_chains).  One stream, one batch
+    // a launch; verify_batches' two-stream overlap goes through verify_group
     static hipError_t verify(gcr_problem* P, const double Tm[2], uint64_t seed, uint64_t s0, uint32_t n,
                              const uint32_t m[2], size_t wg_cap, BatchRecord* rec, hipEvent_t e0, hipEvent_t e1,
-                             hipStream_t s, uint32_t b = 0, uint32_t nb = 1, uint32_t ahead = 1) {
+                             hipStream_t s, uint32_t b = 0, uint32_t nb = 1) {
         GenChain ch;
         Workspace* w = P->w;
+        constexpr uint32_t ahead = 1;
         if (nb > ahead && verify_chains(n) && chain_on()) {
             const uint32_t nbuf = 2 * ahead;
             for (uint32_t k = 0; k < nbuf; ++k) {
@@ -1393,15 +1392,10 @@ struct RectTraits {
                     ch.next_pair = w->pg_pair[(b + ahead) % nbuf].p;
                 }
             }
-            ch.ahead = ahead;
+            ch.next_slot0 = s0 + (uint64_t)ahead * n;
         }
-        const bool set1 = ahead == 2 && (b & 1);
-        if (set1) {
-            w->pf_inc.ensure(n);
-            w->pf_sb.ensure(n);
-        }
-        uint8_t* const inc = set1 ? w->pf_inc.p : w->inc.p;
-        const ScoreOut sb = set1 ? w->pf_sb.dev() : w->sb.dev();
+        uint8_t* const inc = w->inc.p;
+        const ScoreOut sb = w->sb.dev();
         if (!defer_on()) {
             return launch_verify_fused(P->dp, Tm, seed, s0, n, m, inc, P->w->models.p, sb, P->w->wg.p, wg_cap, rec,
                                        e0, e1, s, ch);
@@ -1416,8 +1410,97 @@ struct RectTraits {
         const uint32_t k = b % R;
         hipError_t e = launch_verify_fused(P->dp, Tm, seed, s0, n, m, inc, w->vb_models.p + (size_t)k * n, sb,
                                            w->vb_wg.p + (size_t)k * wg_cap, wg_cap, nullptr, e0, e1, s, ch);
-        if (e != hipSuccess || ahead != 1 || !(k == R - 1 || b + 1 == nb)) return e;
+        if (e != hipSuccess || !(k == R - 1 || b + 1 == nb)) return e;
         return select_flush(P, s0 - (uint64_t)k * n, n, k + 1, wg_cap, rec - k, s);
+    }
+    // verify_batches' two-stream overlap, several batches a launch (the
+    // grouped fused scorer, fm_groups.h).  A call's launches are numbered in
+    // batch order and alternate between two streams; launch L covers batches
+    // [b, b + count), never across the end of a selection ring, so its ring
+    // slots (models, workgroup records) are contiguous.  It takes its first
+    // batch's slots from pre-generation buffer L % 4 (L >= 2: launch L - 2 on
+    // the same stream generated them), generates the first batch of launch
+    // L + 2 (slots from next_s0) into buffer (L + 2) % 4 when has_next, and
+    // writes its per-slot outputs to set L & 1, batch after batch.  The ring's
+    // selection is left to the caller (select_flush), which orders it after
+    // both streams.
+    static void verify_group_buffers(gcr_problem* P, uint32_t n, uint32_t gmax, size_t wg_cap) {
+        Workspace* w = P->w;
+        for (uint32_t k = 0; k < 4; ++k) {
+            w->pg_inc[k].ensure(n);
+            w->pg_models[k].ensure(n);
+            if (preconst_on()) {
+                w->pg_hyp[k].ensure((size_t)n * kFmHypBytes);
+                w->pg_pair[k].ensure((size_t)(n + 1) / 2 * kFmPairBytes);
+            }
+        }
+        w->inc.ensure((size_t)gmax * n);
+        w->sb.ensure((size_t)gmax * n);
+        w->pf_inc.ensure((size_t)gmax * n);
+        w->pf_sb.ensure((size_t)gmax * n);
+        const uint32_t R = select_ring(n);
+        w->vb_wg.ensure((size_t)R * wg_cap);
+        w->vb_models.ensure((size_t)R * n);
+    }
+    static hipError_t verify_group(gcr_problem* P, const double Tm[2], uint64_t seed, uint64_t s0, uint32_t n,
+                                   const uint32_t m[2], size_t wg_cap, hipStream_t s, uint32_t L, uint32_t b,
+                                   uint32_t count, bool has_next, uint64_t next_s0, bool stage_a) {
+        Workspace* w = P->w;
+        const bool pc = preconst_on();
+        GenChain ch;
+        if (L >= 2) {
+            ch.pre_inc = w->pg_inc[L % 4].p;
+            ch.pre_models = w->pg_models[L % 4].p;
+            if (pc) {
+                ch.pre_hyp = w->pg_hyp[L % 4].p;
+                ch.pre_pair = w->pg_pair[L % 4].p;
+            }
+        }
+        if (has_next) {
+            ch.next_inc = w->pg_inc[(L + 2) % 4].p;
+            ch.next_models = w->pg_models[(L + 2) % 4].p;
+            if (pc) {
+                ch.next_hyp = w->pg_hyp[(L + 2) % 4].p;
+                ch.next_pair = w->pg_pair[(L + 2) % 4].p;
+            }
+            ch.next_slot0 = next_s0;
+        }
+        const bool set1 = L & 1;
+        uint8_t* const inc = set1 ? w->pf_inc.p : w->inc.p;
+        const ScoreOut sb = set1 ? w->pf_sb.dev() : w->sb.dev();
+        const uint32_t k = b % select_ring(n);
+        FusedGroups grp;
+        grp.groups = count;
+        grp.slot_stride = n;
+        grp.models_stride = n;
+        grp.wg_stride = (uint32_t)wg_cap;
+        grp.stage_a = stage_a;
+        return launch_verify_fused(P->dp, Tm, seed, s0, n, m, inc, w->vb_models.p + (size_t)k * n, sb,
+                                   w->vb_wg.p + (size_t)k * wg_cap, wg_cap, nullptr, nullptr, nullptr, s, ch, grp);
+    }
+    // batches a launch of the overlapped path (G divides the selection ring):
+    // GCR_VERIFY_GROUPS=n (read per call) pins it for A/B runs and tests.
+    // Default 8, the most the kernel takes: M2 at 4096 slots measured 78.3 /
+    // 74.6 / 73.2 / 72.2 us per batch at G = 1 / 2 / 4 / 8 in 2000-batch
+    // calls and 84.6 / 82.8 / 79.1 / 77.8 in 20-batch calls (MEASUREMENTS.md
+    // §1), so a short call keeps the large G too; it is only halved until
+    // the call has two full launches, one for each stream
+    static constexpr uint32_t kVerifyGroups = 8;
+    static uint32_t verify_groups(uint32_t n, uint32_t nb) {
+        const uint32_t R = select_ring(n);
+        const char* e = getenv("GCR_VERIFY_GROUPS");
+        uint32_t G = kVerifyGroups;
+        if (e && atoi(e) >= 1) G = std::min<uint32_t>((uint32_t)atoi(e), fmg::kMaxGroups);
+        else
+            while (G > 1 && nb < 2 * G) G >>= 1;
+        while (G > 1 && R % G != 0) --G;
+        return G;
+    }
+    // GCR_VERIFY_GROUPS_STAGE=a (read per call): the compute waves wait at
+    // every batch boundary of a launch for the chain wave (A/B)
+    static bool verify_groups_stage_a() {
+        const char* e = getenv("GCR_VERIFY_GROUPS_STAGE");
+        return e && e[0] == 'a';
     }
     // the deferred selection of ring batches 0 .. count - 1 (slots from s0):
     // their records to rec[0 .. count)
@@ -2564,25 +2647,39 @@ public:
                 for (hipEvent_t* e : {&w->vb_gen[0], &w->vb_gen[1], &w->vb_start, &w->vb_flush})
                     if (*e == nullptr) HIPC(hipEventCreateWithFlags(e, hipEventDisableTiming));
                 const uint32_t R = Tr::select_ring(nslots);
+                // launches: up to G batches each, clipped at the ring's end
+                // and at nb (fm_groups.h), in batch order
+                const uint32_t G = Tr::verify_groups(nslots, nb);
+                const bool stage_a = Tr::verify_groups_stage_a();
+                std::vector<std::pair<uint32_t, uint32_t>> ln;          // first batch, count
+                for (uint32_t b = 0; b < nb;) {
+                    const uint32_t c = fmg::launch_batches(b, nb, G, R);
+                    ln.emplace_back(b, c);
+                    b += c;
+                }
+                Tr::verify_group_buffers(P_, nslots, G, wg_cap);
                 HIPC(hipEventRecord(P_->w->evs[0], s_));
                 HIPC(hipEventRecord(w->vb_start, s_));
                 HIPC(hipStreamWaitEvent(side, w->vb_start, 0));
                 bool side_wait = false;             // the side stream must wait for the last selection
-                for (uint32_t b = 0; b < nb; ++b) {
-                    const uint32_t k = b % R;
+                for (uint32_t L = 0; L < ln.size(); ++L) {
+                    const uint32_t b = ln[L].first, c = ln[L].second;
+                    const uint32_t last = b + c - 1, k = last % R;
                     const uint64_t s0 = slot0 + (uint64_t)b * nslots;
-                    hipStream_t st = (b & 1) ? side : s_;
-                    if ((b & 1) && side_wait) {
+                    hipStream_t st = (L & 1) ? side : s_;
+                    if ((L & 1) && side_wait) {
                         HIPC(hipStreamWaitEvent(side, w->vb_flush, 0));
                         side_wait = false;
                     }
-                    HIPC(Tr::verify(P_, Tm_, prm_.seed, s0, nslots, m32, wg_cap, drecs + b, nullptr, nullptr, st, b,
-                                    nb, 2));
-                    if (k == R - 1 || b + 1 == nb) {
+                    const bool has_next = L + 2 < ln.size();
+                    const uint64_t next_s0 = has_next ? slot0 + (uint64_t)ln[L + 2].first * nslots : 0;
+                    HIPC(Tr::verify_group(P_, Tm_, prm_.seed, s0, nslots, m32, wg_cap, st, L, b, c, has_next, next_s0,
+                                          stage_a));
+                    if (k == R - 1 || last + 1 == nb) {
                         HIPC(hipEventRecord(w->vb_gen[1], side));
                         HIPC(hipStreamWaitEvent(s_, w->vb_gen[1], 0));
-                        HIPC(Tr::select_flush(P_, s0 - (uint64_t)k * nslots, nslots, k + 1, wg_cap, drecs + (b - k),
-                                              s_));
+                        HIPC(Tr::select_flush(P_, slot0 + (uint64_t)(last - k) * nslots, nslots, k + 1, wg_cap,
+                                              drecs + (last - k), s_));
                         HIPC(hipEventRecord(w->vb_flush, s_));
                         side_wait = true;
                     }

@@ -232,9 +232,9 @@ struct WgBest {
 // the launch's prologue generates them), `next` receives the next batch's
 // (slots slot0 + nslots ...), generated by a dedicated wave while this batch
 // is scored (null: none).  Same models and attempt counts as the prologue.
-// `ahead`: the batch `next` belongs to, counted from this one (2 when
-// consecutive batches alternate between two streams: batch b generates batch
-// b + 2's slots, which the same stream scores next).
+// `next_slot0`: the first slot index of the batch `next` belongs to (with two
+// alternating streams, the first batch of the launch after next, which the
+// same stream scores next).
 // `const` (optional, both or neither): the look-ahead wave also writes each
 // generated slot's band and value constants (HypConst, kFmHypBytes per slot)
 // and its half of the packed-fp32 pre-band record (RPairBand, kFmPairBytes
@@ -246,19 +246,32 @@ struct GenChain {
     const RectModel* pre_models = nullptr;
     uint8_t* next_inc = nullptr;
     RectModel* next_models = nullptr;
-    uint32_t ahead = 1;
+    uint64_t next_slot0 = 0;
     const void* pre_hyp = nullptr;
     const void* pre_pair = nullptr;
     void* next_hyp = nullptr;
     void* next_pair = nullptr;
 };
+// Several consecutive batches in one launch of the feature-major fused scorer
+// (fm_groups.h): workgroup i stays resident and scores its 16 slots of batch
+// g = 0 .. groups - 1 (slots slot0 + g nslots + 16 i ...) one after the other.
+// Batch g's per-slot outputs (inc and every ScoreOut array) lie slot_stride
+// entries after batch g - 1's, its models models_stride and its workgroup
+// records wg_stride entries after.  stage_a (A/B): the compute waves wait at
+// each batch boundary until the chain wave has written the batch before.
+struct FusedGroups {
+    uint32_t groups = 1;
+    uint32_t slot_stride = 0, models_stride = 0, wg_stride = 0;
+    bool stage_a = false;
+};
 // rec == nullptr: the launch leaves its workgroup records in `wg` (and its
 // models in `models`) for a later launch_select_batches instead of reducing
-// them right away
+// them right away (required when grp.groups > 1)
 hipError_t launch_verify_fused(const DevProblem& p, const double T[2], uint64_t seed, uint64_t slot0,
                                uint32_t nslots, const uint32_t m[2], uint8_t* inc, RectModel* models,
                                const ScoreOut& out, WgBest* wg, size_t wg_cap, BatchRecord* rec,
-                               hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream, const GenChain& chain = {});
+                               hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream, const GenChain& chain = {},
+                               const FusedGroups& grp = {});
 // Deferred selection of `count` consecutive fused batches in one launch (one
 // workgroup per batch): batch i's workgroup records at wg + i * wg_stride,
 // its models at models + i * nslots, its slots from slot0 + i * nslots, its

@@ -14,6 +14,7 @@
 // Compiled with -ffp-contract=off: every fp64 expression rounds exactly like
 // the host restatement.
 #include "kernels.h"
+#include "fm_groups.h"
 #include "philox.h"
 #include "qr3.h"
 
@@ -490,9 +491,16 @@ struct GenArgs {
     // prologue's attempts (every slot takes attempt 0's default model)
     // k_score_fm: bit 8 no wait for the chain before the exact pass, bit 9
     // no inlier-count atomics; valid A/B: bit 10 the rectification fp64
-    // bands instead of the packed fp32 pre-band
+    // bands instead of the packed fp32 pre-band.  The bits k_score_fm tests
+    // inside its round loops exist only with -DGCR_FM_PROBES (fm_probe)
     uint32_t probe;
     GenChain chain;                     // k_score_fm<.., true>: batch chaining
+    // k_score_fm<.., 16, true>: batches ("groups") per launch, 1 .. fmg::kMaxGroups,
+    // and group g's offsets from group g - 1 in inc and the ScoreOut arrays,
+    // in models and in wg (FusedGroups, kernels.h)
+    uint32_t groups;
+    uint32_t slot_stride, models_stride, wg_stride;
+    bool stage_a;
     // k_score_fm, KIND >= 3: compact in the prologue instead of k_compact --
     // every workgroup scans scan_inc[0 .. nh) (live: <= 101) and scores live
     // ranks [blockIdx.x H, + H); hmap / hcount are then written, not read
@@ -978,6 +986,16 @@ __device__ __forceinline__ uint32_t write_lane(uint32_t v, uint32_t c) {
     return v;
 }
 
+// GCR_PROBE bits tested inside k_score_fm's round loops (1, 2, 4, 32, 64,
+// 256, 512, 1024): compiled in only with -DGCR_FM_PROBES (make variant,
+// tools/probe_fm.sh).  The product build keeps neither their branches nor the
+// register that holds the bits across the loops.
+#ifdef GCR_FM_PROBES
+__device__ __forceinline__ bool fm_probe(uint32_t bits, uint32_t bit) { return (bits & bit) != 0; }
+#else
+__device__ __forceinline__ constexpr bool fm_probe(uint32_t, uint32_t) { return false; }
+#endif
+
 constexpr int kFmWaves = 15;
 constexpr int kFmCB = 8;            // chain batch: 16-byte LDS reads (2 values each) per run step
                                     // (16, i.e. 32-value batches: 130.8 vs 127.8 us)
@@ -1178,8 +1196,9 @@ struct RPairBand {                 // hypotheses 2 j (.x) and 2 j + 1 (.y)
 static_assert(sizeof(RPairBand) == 16 * 8, "RPairBand layout: 16 float pairs");
 
 static_assert(sizeof(HypConst) == kFmHypBytes && sizeof(RPairBand) == kFmPairBytes, "GenChain constant records");
-__device__ __forceinline__ void rpb_setup(RPairBand* rp, int t, const HypConst& q, const DevClass& c0,
-                                          const DevClass& c1, double tan_tau1, bool orient, bool valid) {
+// am0, am1: the two classes' largest |x|, |y| (DevClass::amax)
+__device__ __forceinline__ void rpb_setup(RPairBand* rp, int t, const HypConst& q, const double* am0,
+                                          const double* am1, double tan_tau1, bool orient, bool valid) {
     constexpr double u = 0x1p-24;
     float* b = reinterpret_cast<float*>(&rp[t >> 1]);
     const int hf = t & 1;                    // this thread's 4-byte half of each pair
@@ -1195,7 +1214,7 @@ __device__ __forceinline__ void rpb_setup(RPairBand* rp, int t, const HypConst& 
     }
     const double a7 = __builtin_fabs(q.h7), a8 = __builtin_fabs(q.h8);
     {
-        const double X = c0.amax[0], Y = c0.amax[1];
+        const double X = am0[0], Y = am0[1];
         const double tb = 6.0 * u * ((a7 * X + a8 * Y) + 1.0) + (X + Y) * 0x1p-140;
         b[2 * 0 + hf] = (float)(-q.h7);
         b[2 * 1 + hf] = (float)(-q.h8);
@@ -1206,7 +1225,7 @@ __device__ __forceinline__ void rpb_setup(RPairBand* rp, int t, const HypConst& 
         b[2 * 4 + hf] = hi_ok ? (float)(q.hi * (1.0 + 0x1p-19)) : __builtin_inff();
     }
     if (orient) {
-        const double G = c1.amax[0] + c1.amax[1];
+        const double G = am1[0] + am1[1];
         const double e = 32.0 * u * (G * __builtin_fmax(a7, a8) + 1.0) + G * 0x1p-140 + 0x1p-90;
         const double tq = tan_tau1 * (1.0 + 0x1p-18);
         b[2 * 5 + hf] = (float)q.h7;
@@ -1290,26 +1309,41 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
         kDyn ? reinterpret_cast<uint16_t (*)[kQStride]>(fm_dyn_lds + (size_t)kW * H * (kReg / 2)) : queue_st;
     __shared__ uint32_t wcnt[2][kW][H];                 // survivors of (wave, q) in the round
     __shared__ uint32_t ready[kW], done[kW];
-    __shared__ HypConst hyp[H];
-    __shared__ uint32_t hval[H];
-    __shared__ uint32_t cnt_sh[2][H];
-    __shared__ uint32_t fl_sh[H];                       // flagged pairs (exact.h), rectification solvers
     using PairBand = std::conditional_t<KIND == 3, HPairBand, FPairBand>;
     static_assert(KIND >= 3 || (H & 1) == 0, "rectification pre-band: hypotheses in pairs");
     static_assert(sizeof(PairBand) == sizeof(RPairBand), "pair-band records share one LDS array");
-    // the correspondence pre-band records or the rectification ones
-    __shared__ RPairBand pb_st[(H + 1) / 2];
-    PairBand* const fpb = reinterpret_cast<PairBand*>(pb_st);
-    RPairBand* const rpb = pb_st;
+    // One group's constants and counters.  The fused variant (kGen) scores
+    // gen.groups batches ("groups") in a launch and keeps two sets, group g in
+    // set g & 1 (fm_groups.h): while group g is scored, the look-ahead wave
+    // fills the other set with group g + 1's generated slots (gen_a, gen_m)
+    // and their constants.
+    struct GSet {
+        // the correspondence pre-band records or the rectification ones
+        // (first: the band reads every field of every record with one base
+        // register and a two-address LDS read's small immediate offsets)
+        RPairBand pb[(H + 1) / 2];
+        HypConst hyp[H];
+        uint32_t hval[H];
+        uint32_t cnt[2][H];
+        uint32_t fl[H];                                 // flagged pairs (exact.h), rectification solvers
+        int gen_a[kGen ? H : 1];
+        RectModel gen_m[kGen ? H : 1];
+        double fin[kGen ? H : 1];
+    };
+    constexpr int kSets = kGen ? 2 : 1;
+    __shared__ GSet gset[kSets];
+    // cons_ready: groups whose set is filled (group g readable at g + 1);
+    // groups_done: groups whose outputs the chain wave has written.  Both
+    // only grow (fm_groups.h)
+    __shared__ uint32_t cons_ready, groups_done;
     // the value log's table (detmath.h) in LDS: the fused variant has the
     // room (the others read it from L2)
     __shared__ double logtab_sh[kGen ? dm::kLogTabSize : 1];
-    __shared__ int gen_a[kGen ? H : 1];
-    __shared__ RectModel gen_m[kGen ? H : 1];
-    __shared__ double fin_sh[kGen ? H : 1];
-    // the look-ahead wave's generated slots (models, attempts)
-    __shared__ RectModel nx_m[kGen ? H : 1];
-    __shared__ int nx_a[kGen ? H : 1];
+    const uint32_t groups = kGen ? gen.groups : 1u;
+    // the current group's set: the prologue below fills set 0 (group 0)
+    GSet* cs = &gset[0];
+    auto use_set = [&](uint32_t g) { cs = &gset[kGen ? fmg::set_of(g) : 0u]; };
+    auto fpb_of = [](GSet* s) { return reinterpret_cast<PairBand*>(s->pb); };
 
     const int t = threadIdx.x;
     const int wave = t >> 6;
@@ -1411,8 +1445,8 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             const uint32_t hs = blockIdx.x * H + t;
             const uint8_t iv = hs < nh ? gen.chain.pre_inc[hs] : (uint8_t)102;
             const RectModel m = iv > 101 ? default_model() : gen.chain.pre_models[hs];
-            gen_a[t] = iv > 101 ? 127 : (int)iv - 1;
-            gen_m[t] = m;
+            cs->gen_a[t] = iv > 101 ? 127 : (int)iv - 1;
+            cs->gen_m[t] = m;
             if (hs < nh) {
                 gen.inc[hs] = iv;
                 gen.models[hs] = m;
@@ -1421,7 +1455,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
       } else {
         const int G = gen.glanes ? (int)gen.glanes : kSplitThreads / H;
         const bool gact = t < H * G;
-        if (t < H) gen_a[t] = 127;
+        if (t < H) cs->gen_a[t] = 127;
         __syncthreads();
         const int gh = gact ? t / G : 0, g = t % G;
         const uint32_t gs = blockIdx.x * H + gh;
@@ -1429,30 +1463,30 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             const uint32_t a = rr * G + g;
             RectModel m = default_model();
             bool ok = false;
-            if (gact && gs < nh && a < 101 && gen_a[gh] == 127)
+            if (gact && gs < nh && a < 101 && cs->gen_a[gh] == 127)
                 ok = (gen.probe & 8u) ? a == 0 : attempt<KIND>(p, gen.seed, gen.slot0 + gs, a, m);
-            if (ok) atomicMin(&gen_a[gh], (int)a);
+            if (ok) atomicMin(&cs->gen_a[gh], (int)a);
             __syncthreads();
-            if (ok && gen_a[gh] == (int)a) gen_m[gh] = m;
+            if (ok && cs->gen_a[gh] == (int)a) cs->gen_m[gh] = m;
             bool all = true;
-            for (int q = 0; q < H; ++q) all = all && (gen_a[q] != 127 || blockIdx.x * H + q >= nh);
+            for (int q = 0; q < H; ++q) all = all && (cs->gen_a[q] != 127 || blockIdx.x * H + q >= nh);
             __syncthreads();
             if (all) break;
         }
         if (t < H && blockIdx.x * H + t < nh) {
-            const int a = gen_a[t];
+            const int a = cs->gen_a[t];
             gen.inc[blockIdx.x * H + t] = (uint8_t)(a == 127 ? 102 : a + 1);
-            gen.models[blockIdx.x * H + t] = a == 127 ? default_model() : gen_m[t];
+            gen.models[blockIdx.x * H + t] = a == 127 ? default_model() : cs->gen_m[t];
         }
       }
     }
     if (t < H) {
         const uint32_t hg = blockIdx.x * H + t;
         const uint32_t mi = (KIND >= 3 && gen.hmap != nullptr && hg < nh) ? smap[t] : hg;
-        const bool v = hg < nh && (kGen ? gen_a[t] != 127 : (inc == nullptr || inc[mi] <= 101));
+        const bool v = hg < nh && (kGen ? cs->gen_a[t] != 127 : (inc == nullptr || inc[mi] <= 101));
         typename ModelOf<KIND>::type m = ModelOf<KIND>::def();
         if (v) {
-            if constexpr (kGen && KIND < 3) m = gen_m[t];
+            if constexpr (kGen && KIND < 3) m = cs->gen_m[t];
             else m = models[mi];
         }
         bool copied = false;
@@ -1460,31 +1494,31 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             // constants the previous launch's look-ahead wave computed for
             // this slot (the same make_hyp / rpb_setup of the same model)
             if (gen.chain.pre_inc != nullptr && gen.chain.pre_hyp != nullptr && hg < nh) {
-                hyp[t] = static_cast<const HypConst*>(gen.chain.pre_hyp)[hg];
+                cs->hyp[t] = static_cast<const HypConst*>(gen.chain.pre_hyp)[hg];
                 const float* src = reinterpret_cast<const float*>(static_cast<const RPairBand*>(gen.chain.pre_pair) +
                                                                   (hg >> 1));
-                float* dst = reinterpret_cast<float*>(&rpb[t >> 1]);
+                float* dst = reinterpret_cast<float*>(&cs->pb[t >> 1]);
 #pragma unroll
                 for (int k = 0; k < 11; ++k) dst[2 * k + (t & 1)] = src[2 * k + (hg & 1)];
                 copied = true;
             }
         }
         if (!copied) {
-            hyp[t] = make_hyp<KIND>(m, band0);
-            if constexpr (KIND <= 2) rpb_setup(rpb, t, hyp[t], p.cls[0], p.cls[1], tan_tau1, KIND == 2, v);
+            cs->hyp[t] = make_hyp<KIND>(m, band0);
+            if constexpr (KIND <= 2) rpb_setup(cs->pb, t, cs->hyp[t], p.cls[0].amax, p.cls[1].amax, tan_tau1, KIND == 2, v);
         }
-        if constexpr (KIND == 4) fpb_setup(fpb, t, m.h, v, T0, p.cls[0]);
-        if constexpr (KIND == 3) hpb_setup(fpb, t, m.h, v, band0, p.cls[0]);
-        hval[t] = v ? 1u : 0u;
-        cnt_sh[0][t] = 0;
-        cnt_sh[1][t] = 0;
-        fl_sh[t] = 0;
+        if constexpr (KIND == 4) fpb_setup(fpb_of(cs), t, m.h, v, T0, p.cls[0]);
+        if constexpr (KIND == 3) hpb_setup(fpb_of(cs), t, m.h, v, band0, p.cls[0]);
+        cs->hval[t] = v ? 1u : 0u;
+        cs->cnt[0][t] = 0;
+        cs->cnt[1][t] = 0;
+        cs->fl[t] = 0;
     }
     if constexpr (KIND == 4) {
-        if ((H & 1) && t == H) fpb_setup(fpb, t, hyp[0].g, false, T0, p.cls[0]);   // odd H: inert pad
+        if ((H & 1) && t == H) fpb_setup(fpb_of(cs), t, cs->hyp[0].g, false, T0, p.cls[0]);   // odd H: inert pad
     }
     if constexpr (KIND == 3) {
-        if ((H & 1) && t == H) hpb_setup(fpb, t, hyp[0].g, false, band0, p.cls[0]);
+        if ((H & 1) && t == H) hpb_setup(fpb_of(cs), t, cs->hyp[0].g, false, band0, p.cls[0]);
     }
     GCR_STAMP(6, 15u);
     if constexpr (kGen) {
@@ -1492,6 +1526,10 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
     }
     const double* const logtab = kGen ? logtab_sh : dm::kLogTab;
     if (t < kW) { ready[t] = 0; done[t] = 0; }
+    if (t == 0) {
+        cons_ready = fmg::cons_ready_for(0);
+        groups_done = 0;
+    }
     __syncthreads();
     GCR_STAMP(7, 15u);
 
@@ -1499,7 +1537,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
         if (wave == kW) {
             // ------------------------------------------ look-ahead generator
             // the next batch's slots of this workgroup (blockIdx.x * H + sl,
-            // slot index slot0 + ahead nh + ...), k_generate_fw's widening lane
+            // slot indices from nslot0), k_generate_fw's widening lane
             // groups: the H slots start with 64 / H lanes each, and after
             // every round the unfinished ones share the whole wave (64 /
             // pow2ceil(k) lanes for k left) from one wave-uniform lowest
@@ -1508,9 +1546,36 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             // 50 % outliers: fixed groups of 4 lanes needed 3-5 rounds of
             // attempt latency for the slowest of 16 slots, widening ~2-3.
             // Overlaps the rounds below; no barrier follows.
-            if (gen.chain.next_inc == nullptr) return;
+            //
+            // Groups (fm_groups.h): pass gn = 1 .. groups - 1 generates group
+            // gn of this launch into LDS set gn & 1 (models, attempts, the
+            // make_hyp / rpb_setup constants, cleared counters) and writes
+            // the group's inc / models outputs; the last pass, gn = groups,
+            // generates the next launch's first group into the global
+            // pre-generation buffers, with that set as scratch.  A set is
+            // overwritten only once the chain wave has written the outputs of
+            // the group that used it (groups_done).
             const uint32_t hs0 = blockIdx.x * H;
             const uint32_t live = hs0 < nh ? min((uint32_t)H, nh - hs0) : 0u;
+          for (uint32_t gn = 1; gn <= groups; ++gn) {
+            const bool inner = gn < groups;
+            if (!inner && gen.chain.next_inc == nullptr) return;
+            while (__hip_atomic_load(&groups_done, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) <
+                   fmg::set_free_for(gn))
+                __builtin_amdgcn_s_sleep(16);
+            GSet& ns = gset[fmg::set_of(gn)];
+            // the constants' inputs, opaque per pass: their derived values
+            // (1 / band0, the error bounds of rpb_setup) are recomputed in
+            // each pass instead of being kept -- spilled -- across the loop
+            double l_band0 = band0, l_tan = tan_tau1;
+            double l_am[4] = {p.cls[0].amax[0], p.cls[0].amax[1], p.cls[1].amax[0], p.cls[1].amax[1]};
+            asm volatile("" : "+s"(l_band0), "+s"(l_tan), "+s"(l_am[0]), "+s"(l_am[1]), "+s"(l_am[2]), "+s"(l_am[3]));
+            RectModel* const nx_m = ns.gen_m;
+            int* const nx_a = ns.gen_a;
+            const uint64_t nslot0 = inner ? fmg::slot_of(gen.slot0, gn, nh, blockIdx.x, H, 0)
+                                          : gen.chain.next_slot0 + hs0;
+            uint8_t* const o_inc = inner ? gen.inc + (size_t)gn * gen.slot_stride : gen.chain.next_inc;
+            RectModel* const o_models = inner ? gen.models + (size_t)gn * gen.models_stride : gen.chain.next_models;
             uint64_t pend = live >= 64u ? ~0ull : (1ull << live) - 1ull;
             uint32_t nx = 0;                    // wave-uniform lowest untried attempt
             while (pend) {
@@ -1531,7 +1596,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 bool ok = false;
                 if (si >= 0 && a < 101)
                     ok = (gen.probe & 8u) ? a == 0
-                                          : attempt<KIND>(p, gen.seed, gen.slot0 + (uint64_t)gen.chain.ahead * nh + hs0 + (uint32_t)si, a, m);
+                                          : attempt<KIND>(p, gen.seed, nslot0 + (uint32_t)si, a, m);
                 const uint64_t mask = __ballot(ok);
                 nx += 1u << lw;
                 const bool out_of_attempts = nx >= 101;
@@ -1555,52 +1620,83 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 pend = np;
                 const uint32_t hs = hs0 + (uint32_t)si;
                 if (win) {
-                    gen.chain.next_inc[hs] = (uint8_t)(a + 1);
-                    gen.chain.next_models[hs] = m;
+                    o_inc[hs] = (uint8_t)(a + 1);
+                    o_models[hs] = m;
                     nx_m[si] = m;
                     nx_a[si] = (int)a;
                 } else if (fail) {              // every attempt failed (inc 102, no model)
-                    gen.chain.next_inc[hs] = 102;
-                    gen.chain.next_models[hs] = default_model();
+                    o_inc[hs] = 102;
+                    o_models[hs] = default_model();
                     nx_a[si] = 127;
                 }
             }
-            if (gen.chain.next_hyp == nullptr) return;
-            // the slots' constants for the next launch's prologue (make_hyp
-            // and rpb_setup as the prologue would run them), one lane a slot
+            if (!inner && gen.chain.next_hyp == nullptr) return;
+            // the slots' constants (make_hyp and rpb_setup as the prologue
+            // would run them), one lane a slot: group gn's into its set, as
+            // the prologue leaves set 0 for group 0 (slots past the launch's
+            // count are inert), or the next launch's for its prologue to copy
             __builtin_amdgcn_wave_barrier();
-            if (lane < (int)live) {
+            if (inner) {
+                if (lane < H) {
+                    const bool v = lane < (int)live && nx_a[lane] != 127;
+                    const RectModel m = v ? nx_m[lane] : default_model();
+                    if (!v) {
+                        nx_a[lane] = 127;
+                        nx_m[lane] = m;
+                    }
+                    const HypConst q = make_hyp<KIND>(m, l_band0);
+                    ns.hyp[lane] = q;
+                    rpb_setup(ns.pb, lane, q, l_am, l_am + 2, l_tan, KIND == 2, v);
+                    ns.hval[lane] = v ? 1u : 0u;
+                    ns.cnt[0][lane] = 0;
+                    ns.cnt[1][lane] = 0;
+                    ns.fl[lane] = 0;
+                }
+                fm_publish(&cons_ready, fmg::cons_ready_for(gn));
+            } else if (lane < (int)live) {
                 const bool v = nx_a[lane] != 127;
                 const RectModel m = v ? nx_m[lane] : default_model();
-                const HypConst q = make_hyp<KIND>(m, band0);
+                const HypConst q = make_hyp<KIND>(m, l_band0);
                 static_cast<HypConst*>(gen.chain.next_hyp)[hs0 + (uint32_t)lane] = q;
-                rpb_setup(static_cast<RPairBand*>(gen.chain.next_pair) + (hs0 >> 1), lane, q, p.cls[0], p.cls[1],
-                          tan_tau1, KIND == 2, v);
+                rpb_setup(static_cast<RPairBand*>(gen.chain.next_pair) + (hs0 >> 1), lane, q, l_am, l_am + 2, l_tan,
+                          KIND == 2, v);
             }
+          }
             return;
         }
     }
 
     if (!chain_wave) {
         // ---------------------------------------------------- compute waves
-        uint64_t vmask = __ballot(lane < H && hval[lane < H ? lane : 0] != 0);
-        if (gen.probe & 4u) vmask = 0;
         uint16_t* qw = queue[wave];
         double nxt[4];
         bool nok = false;
         if (rounds > 0) load(0, nxt, nok);
+      for (uint32_t g = 0; g < groups; ++g) {
+        if (kGen && g > 0) {
+            // group g's constants are in its set (the look-ahead wave);
+            // stage (a): the chain wave has also written group g - 1's outputs
+            if (gen.stage_a) fm_wait_ge(&groups_done, fmg::boundary_wait(g));
+            fm_wait_ge(&cons_ready, fmg::cons_ready_for(g));
+            use_set(g);
+        }
+        uint64_t vmask = __ballot(lane < H && cs->hval[lane < H ? lane : 0] != 0);
+        if (fm_probe(gen.probe, 4u)) vmask = 0;
         for (uint32_t r = 0; r < rounds; ++r) {
-            GCR_STAMP(0, r);
+            // the flags' round number runs on across the groups (fm_groups.h)
+            const uint32_t gr = kGen ? fmg::global_round(g, rounds, r) : r;
+            GCR_STAMP(0, gr);
             const double f0 = nxt[0], f1 = nxt[1], f2 = nxt[2], f3 = nxt[3];
             const bool ok = nok;
             if (r + 1 < rounds) load(r + 1, nxt, nok);
+            else if (kGen && g + 1 < groups) load(0, nxt, nok);   // the next group's first round
             const int cls = r < r0 ? 0 : 1;
             // 1) band test against each hypothesis.  Each lane holds one
             //    feature, so q's survivors are one ballot: survivor k of q (in
             //    feature order) owns slot k of the region outv[wave][q], and
             //    the queue entry q | lane << 4 | k << 10 carries all of it
             uint32_t qn = 0, my_n = 0;
-            uint32_t* wc = wcnt[r & 1][wave];
+            uint32_t* wc = wcnt[fmg::round_parity(gr)][wave];
             // one fully unrolled hypothesis loop per band (the class is
             // uniform over a round): no class branch per q, the band itself
             // branch-free and evaluated on every lane (out-of-range lanes
@@ -1638,7 +1734,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     for (int q = 0; q < H; q += 2) {
                         if (!((vmask >> q) & 3ull)) continue;
                         bool rj[2];
-                        pb_test(fpb[q >> 1], x1, y1, x2, y2, rj[0], rj[1]);
+                        pb_test(fpb_of(cs)[q >> 1], x1, y1, x2, y2, rj[0], rj[1]);
 #pragma unroll
                         for (int o = 0; o < 2; ++o) {
                             const int qq = q + o;
@@ -1659,7 +1755,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
 #pragma unroll 1
                     for (int q = 0; q < H; ++q) {
                         if (!((vmask >> q) & 1ull)) continue;
-                        const bool cand = ok & geo_band<KIND>(f0, f1, f2, f3, hyp[q].g, band0);
+                        const bool cand = ok & geo_band<KIND>(f0, f1, f2, f3, cs->hyp[q].g, band0);
                         const uint64_t m = __builtin_amdgcn_ballot_w64(cand);
                         const uint32_t k = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32),
                                                                      __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
@@ -1669,10 +1765,10 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                         qn += c;
                     }
                 }
-                } else if (!(gen.probe & 1024u)) {
+                } else if (!fm_probe(gen.probe, 1024u)) {
                     // rectification: the packed fp32 pre-band (above), two
                     // hypotheses per pass; every mask a direct compare ballot
-                    const uint64_t okm = (gen.probe & 4u) ? 0ull : __builtin_amdgcn_ballot_w64(ok);
+                    const uint64_t okm = fm_probe(gen.probe, 4u) ? 0ull : __builtin_amdgcn_ballot_w64(ok);
                     float pa = 0.0f, pb = 0.0f, pc = 0.0f;
                     if (cls == 0) {
                         pa = (float)f0;
@@ -1703,11 +1799,11 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     // the next pair's constants are read before this pair's
                     // queue writes (the reads cannot be moved across them)
                     if (cls == 0) {
-                        RScaleC cur = rpb_scale_c(rpb[0]);
+                        RScaleC cur = rpb_scale_c(cs->pb[0]);
                         static_for<0, H / 2>([&](auto jc) {
                             constexpr int j = decltype(jc)::value;
                             RScaleC nxt = cur;
-                            if constexpr (j + 1 < H / 2) nxt = rpb_scale_c(rpb[j + 1]);
+                            if constexpr (j + 1 < H / 2) nxt = rpb_scale_c(cs->pb[j + 1]);
                             uint64_t r0, r1;
                             rpb_scale(cur, pa, pb, pc, r0, r1);
                             emit(std::integral_constant<int, 2 * j>{}, r0);
@@ -1715,11 +1811,11 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                             cur = nxt;
                         });
                     } else {
-                        ROrientC cur = rpb_orient_c(rpb[0]);
+                        ROrientC cur = rpb_orient_c(cs->pb[0]);
                         static_for<0, H / 2>([&](auto jc) {
                             constexpr int j = decltype(jc)::value;
                             ROrientC nxt = cur;
-                            if constexpr (j + 1 < H / 2) nxt = rpb_orient_c(rpb[j + 1]);
+                            if constexpr (j + 1 < H / 2) nxt = rpb_orient_c(cs->pb[j + 1]);
                             uint64_t r0, r1;
                             rpb_orient(cur, pa, pb, pc, r0, r1);
                             emit(std::integral_constant<int, 2 * j>{}, r0);
@@ -1728,14 +1824,14 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                         });
                     }
                 } else if (cls == 0) {
-                    run_band([&](int q) { return C4{hyp[q].h7, hyp[q].h8, hyp[q].lo, hyp[q].hi}; },
+                    run_band([&](int q) { return C4{cs->hyp[q].h7, cs->hyp[q].h8, cs->hyp[q].lo, cs->hyp[q].hi}; },
                              [&](const C4& c) {
                                  HypConst hq;
                                  hq.h7 = c.a; hq.h8 = c.b; hq.lo = c.c; hq.hi = c.d;
                                  return scale_band<KIND>(f0, f1, f2, hq);
                              });
                 } else if constexpr (KIND == 2) {
-                    run_band([&](int q) { return C4{hyp[q].h7, hyp[q].h8, hyp[q].cf, hyp[q].sf}; },
+                    run_band([&](int q) { return C4{cs->hyp[q].h7, cs->hyp[q].h8, cs->hyp[q].cf, cs->hyp[q].sf}; },
                              [&](const C4& c) {
                                  HypConst hq;
                                  hq.h7 = c.a; hq.h8 = c.b; hq.cf = c.c; hq.sf = c.d;
@@ -1743,9 +1839,9 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                              });
                 }
             }
-            if (gen.probe & 2u) qn = my_n = 0;
+            if (fm_probe(gen.probe, 2u)) qn = my_n = 0;
             if (lane < H) wc[lane] = my_n;                 // survivors (run length) of (wave, q)
-            GCR_STAMP(1, r);
+            GCR_STAMP(1, gr);
             // 2) + 3) exact residuals of the survivors, all 64 lanes busy: -r^2
             //    for an inlier, +0.0 (an exact no-op of the sum) otherwise.
             //    Each 64-survivor batch's queue entries and features are
@@ -1774,7 +1870,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 sv.e = j < qn ? qw[j] : 0u;
                 const int src = (int)((sv.e >> 4) & 63u);
                 sv.a3 = 0.0;
-                if (gen.probe & 32u) {
+                if (fm_probe(gen.probe, 32u)) {
                     // the survivor's feature from its owner lane (LDS permute)
                     sv.x = __shfl(f0, src);
                     sv.y = __shfl(f1, src);
@@ -1790,7 +1886,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 }
 #ifdef GCR_FM_HQ_AHEAD
                 if constexpr (KIND <= 2) {
-                    const HypConst& hq = hyp[sv.e & 15u];
+                    const HypConst& hq = cs->hyp[sv.e & 15u];
                     sv.h7 = hq.h7;
                     sv.h8 = hq.h8;
                     if (cls == 0) {
@@ -1808,12 +1904,12 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 return sv;
             };
             // GCR_PROBE bit 6: no look-ahead (each batch fetched when used)
-            const bool ahead = KIND < 3 && !(gen.probe & 64u);     // (registers, see above)
+            const bool ahead = KIND < 3 && !fm_probe(gen.probe, 64u);     // (registers, see above)
             Surv cur{};
             if (ahead && qn > 0) cur = fetch(0);
             // the chain has folded this wave's previous runs (outv reuse)
-            if (r > 0 && !(gen.probe & 256u)) fm_wait_ge(&done[wave], r);
-            GCR_STAMP(2, r);
+            if (gr > 0 && !fm_probe(gen.probe, 256u)) fm_wait_ge(&done[wave], fmg::region_free(gr));
+            GCR_STAMP(2, gr);
             double* ow = reinterpret_cast<double*>(&outv[wave][0][0]);
             for (uint32_t j0 = 0; j0 < qn; j0 += 64) {
                 if (!ahead) cur = fetch(j0);
@@ -1823,7 +1919,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 const int q = (int)(cur.e & 15u);
                 const uint32_t k = cur.e >> 10;
                 if (v) {
-                    const HypConst& hq = hyp[q];
+                    const HypConst& hq = cs->hyp[q];
                     double r2;
                     bool inl;
                     if constexpr (KIND >= 3) {
@@ -1854,14 +1950,14 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
 #endif
                     }
                     ow[q * kReg + k] = inl ? -r2 : 0.0;
-                    if (inl && !(gen.probe & 512u)) atomicAdd(&cnt_sh[cls][q], 1u);
+                    if (inl && !fm_probe(gen.probe, 512u)) atomicAdd(&cs->cnt[cls][q], 1u);
                     // a decision the host rechecks with glibc (exact.h); rare
-                    if (KIND <= 2 && in_flag_band(r2, fl_mid, fl_half)) atomicAdd(&fl_sh[q], 1u);
+                    if (KIND <= 2 && in_flag_band(r2, fl_mid, fl_half)) atomicAdd(&cs->fl[q], 1u);
                 }
                 cur = nxt_s;
             }
-            GCR_STAMP(3, r);
-            GCR_STAMP_VAL(6, r, (uint64_t)qn);
+            GCR_STAMP(3, gr);
+            GCR_STAMP_VAL(6, gr, (uint64_t)qn);
 #ifdef GCR_STAMPS
             if (lane == 0 && blockIdx.x < (uint32_t)kSpanWG) atomicAdd((unsigned long long*)&g_wgspan[blockIdx.x][2], (unsigned long long)qn);
 #endif
@@ -1876,9 +1972,10 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     if (s < end) ow[q * kReg + s] = 0.0;
                 }
             }
-            fm_publish(&ready[wave], r + 1);
-            GCR_STAMP(4, r);
+            fm_publish(&ready[wave], fmg::published(gr));
+            GCR_STAMP(4, gr);
         }
+      }
     } else {
         // ------------------------------------------------------- chain wave
         __builtin_amdgcn_s_setprio(3);
@@ -1887,21 +1984,25 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
         const int h = lane % H;
         const int role = kTot ? lane / H : 0;
         const bool chain_lane = lane < (kTot ? 2 * H : H);
-        double run = 0.0, hold = 0.0;
         uint32_t c0 = 0, c1 = 0;
-        const bool fold_on = !(gen.probe & 1u) && chain_lane;
+        const bool fold_on = !fm_probe(gen.probe, 1u) && chain_lane;
+      for (uint32_t g = 0; g < groups; ++g) {
+        // every group's sums start afresh; its outputs go to the group's
+        // part of the per-slot arrays and of wg (GenArgs strides)
+        double run = 0.0, hold = 0.0;
         for (uint32_t r = 0; r < rounds; ++r) {
+            const uint32_t gr = kGen ? fmg::global_round(g, rounds, r) : r;
             if (KIND == 2 && r == r0 && role == 0) {      // first orientation round
                 hold = run;
                 run = 0.0;
             }
-            GCR_STAMP(0, r);
+            GCR_STAMP(0, gr);
             // waves that have published round r (bit w), polled all at once
             auto poll = [&]() -> uint64_t {
                 const uint32_t f = lane < kW
                                        ? __hip_atomic_load(&ready[lane], __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)
                                        : 0u;
-                return __ballot(lane < kW && f >= r + 1);
+                return __ballot(lane < kW && f >= fmg::published(gr));
             };
             uint64_t rmask = poll();
             uint32_t n = 0;
@@ -1912,10 +2013,10 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     __builtin_amdgcn_s_sleep(1);
                     rmask = poll();
                 }
-                if (!have) n = wcnt[r & 1][w][h];
+                if (!have) n = wcnt[fmg::round_parity(gr)][w][h];
                 // the next run's length, read ahead if that wave has published
                 const bool nhave = w + 1 < kW && ((rmask >> (w + 1)) & 1ull);
-                const uint32_t nn = nhave ? wcnt[r & 1][w + 1][h] : 0u;
+                const uint32_t nn = nhave ? wcnt[fmg::round_parity(gr)][w + 1][h] : 0u;
                 if (fold_on) {
                     // whole batches of kFmCB 16-byte reads (zero-padded runs)
                     const double2* reg = outv[w][h];
@@ -1935,30 +2036,36 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     }
                 }
                 // this wave's region is consumed (the adds used every read)
-                __hip_atomic_store(&done[w], r + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_store(&done[w], fmg::published(gr), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 n = nn;
                 have = nhave;
             }
-            GCR_STAMP(4, r);
+            GCR_STAMP(4, gr);
         }
+        if (kGen && g > 0) {
+            // the group's set (already implied by the compute waves' publications)
+            fm_wait_ge(&cons_ready, fmg::cons_ready_for(g));
+            use_set(g);
+        }
+        const size_t go = kGen ? (size_t)g * gen.slot_stride : 0;
         const uint32_t hg = blockIdx.x * H + h;
-        const bool valid_h = hval[h] != 0;
+        const bool valid_h = cs->hval[h] != 0;
         // inlier counts: every compute wave's last atomics precede its final
         // publication, which the loop above has acquired
-        c0 = cnt_sh[0][h];
-        c1 = cnt_sh[1][h];
+        c0 = cs->cnt[0][h];
+        c1 = cs->cnt[1][h];
         double tot = run;
         if constexpr (kTot) tot = __shfl(run, (lane + H) & 63);
         if (lane < H && hg < nh) {
             const double acc0 = KIND == 2 ? hold : run;
             const double acc1 = KIND == 2 ? run : 0.0;
             const uint32_t k0 = valid_h ? c0 : 0, k1 = valid_h ? c1 : 0;
-            out.n0[hg] = k0;
-            out.n1[hg] = k1;
-            out.v0[hg] = valid_h ? acc0 : 0.0;
-            out.v1[hg] = valid_h ? acc1 : 0.0;
-            out.tot[hg] = valid_h ? tot : 0.0;
-            if (KIND <= 2 && out.fl) out.fl[hg] = valid_h ? fl_sh[h] : 0u;
+            out.n0[go + hg] = k0;
+            out.n1[go + hg] = k1;
+            out.v0[go + hg] = valid_h ? acc0 : 0.0;
+            out.v1[go + hg] = valid_h ? acc1 : 0.0;
+            out.tot[go + hg] = valid_h ? tot : 0.0;
+            if (KIND <= 2 && out.fl) out.fl[go + hg] = valid_h ? cs->fl[h] : 0u;
             if constexpr (kGen) {
                 // MSACScoringFunction::getScore finish (MSAC_scoring_function.hpp:108-127)
                 double sum = 0.0;
@@ -1973,8 +2080,8 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                         sum += ms1;
                     }
                 }
-                const bool cand = valid_h && sum > 0.0 && (KIND != 2 || valid_model_sift22(gen_m[h]));
-                fin_sh[h] = cand ? sum : -1.0;
+                const bool cand = valid_h && sum > 0.0 && (KIND != 2 || valid_model_sift22(cs->gen_m[h]));
+                cs->fin[h] = cand ? sum : -1.0;
             }
         }
         if constexpr (kGen) {
@@ -1985,20 +2092,23 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 for (int q = 0; q < H; ++q) {
                     const uint32_t gq = blockIdx.x * H + q;
                     if (gq >= nh) break;
-                    const int a = gen_a[q];
+                    const int a = cs->gen_a[q];
                     b.iterations += (uint64_t)(a == 127 ? 102 : a + 1);
                     if (a != 127) ++b.models;
-                    const double s = fin_sh[q];
+                    const double s = cs->fin[q];
                     if (s > 0.0 && b.score < s) {
                         b.score = s;
                         b.slot = (int32_t)gq;
-                        b.n0 = cnt_sh[0][q];
-                        b.n1 = KIND == 2 ? cnt_sh[1][q] : 0;
+                        b.n0 = cs->cnt[0][q];
+                        b.n1 = KIND == 2 ? cs->cnt[1][q] : 0;
                     }
                 }
-                gen.wg[blockIdx.x] = b;
+                gen.wg[(size_t)g * gen.wg_stride + blockIdx.x] = b;
             }
+            // the set may be refilled (the look-ahead wave waits on this)
+            fm_publish(&groups_done, fmg::outputs_written(g));
         }
+      }
         GCR_WGSPAN(1);
     }
 }
@@ -4607,10 +4717,17 @@ uint32_t probe_bits() {
 hipError_t launch_verify_fused(const DevProblem& p, const double T[2], uint64_t seed, uint64_t slot0,
                                uint32_t nslots, const uint32_t m[2], uint8_t* inc, RectModel* models,
                                const ScoreOut& out, WgBest* wg, size_t wg_cap, BatchRecord* rec,
-                               hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream, const GenChain& chain) {
+                               hipEvent_t ev0, hipEvent_t ev1, hipStream_t stream, const GenChain& chain,
+                               const FusedGroups& grp) {
     if (nslots == 0) return hipErrorInvalidValue;
     const int h = split_h(nslots);
     if ((chain.pre_inc != nullptr || chain.next_inc != nullptr) && !verify_chains(nslots))
+        return hipErrorInvalidValue;
+    // several batches a launch: the chained kernel only, selection deferred,
+    // every group's outputs clear of the group before
+    if (grp.groups < 1 || grp.groups > fmg::kMaxGroups) return hipErrorInvalidValue;
+    if (grp.groups > 1 && (!verify_chains(nslots) || rec != nullptr || grp.slot_stride < nslots ||
+                           grp.models_stride < nslots || grp.wg_stride < (nslots + h - 1) / h))
         return hipErrorInvalidValue;
     const uint32_t nwg = (nslots + h - 1) / h;
     if (nwg > wg_cap) return hipErrorInvalidValue;
@@ -4629,6 +4746,11 @@ hipError_t launch_verify_fused(const DevProblem& p, const double T[2], uint64_t 
     const uint32_t gl = glanes ? glanes : 16u;
     g.glanes = ((1024u / h) % gl == 0 && (gl & (gl - 1)) == 0) ? gl : 0u;
     g.chain = chain;
+    g.groups = grp.groups;
+    g.slot_stride = grp.slot_stride;
+    g.models_stride = grp.models_stride;
+    g.wg_stride = grp.wg_stride;
+    g.stage_a = grp.stage_a;
     if (ev0) (void)hipEventRecord(ev0, stream);
     if (h == 16 && use_fm()) launch_fm_t<16, true>(p, T, nslots, out, g, stream);
     else if (h == 64) launch_fused_t<64, 120>(p, T, nslots, out, g, stream);

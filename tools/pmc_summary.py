@@ -5,6 +5,13 @@ usage: tools/pmc_summary.py gpurun_out/pmc [--slots N --traffic-json profiles/pm
                                            --stats <rocprofv3 kernel_stats.csv of the same command>]
                                            > profiles/<name>.csv
 
+The traffic-json figures are per batch: with several batches scored per
+dispatch (the grouped fused scorer, `--batches-per-dispatch G`: the G the
+profiled command ran with, every dispatch of a long call covers G batches) a
+dispatch's counters and its average duration are divided by G, and the entry
+says so (`batches_per_dispatch`).  bench.py sets these figures against a
+per-batch time.
+
 Each traffic-json entry records the kernel build it was collected from
 (`kernel_build_id`, read from the bench JSON line the passes printed), so
 bench.py never reuses counters of an older build of the kernels.
@@ -53,7 +60,7 @@ def stats_avg_ms(stats_csv):
     return out
 
 
-def main(root, slots=None, traffic_json=None, stats_csv=None):
+def main(root, slots=None, traffic_json=None, stats_csv=None, per=1):
     vals = defaultdict(lambda: defaultdict(list))
     for path in sorted(glob.glob(os.path.join(root, "pass*", "*counter_collection.csv"))):
         with open(path) as f:
@@ -80,19 +87,21 @@ def main(root, slots=None, traffic_json=None, stats_csv=None):
         for k in vals:
             if "FETCH_SIZE" not in vals[k] or not k.startswith("k_score"):
                 continue
-            rd = 2048 * sum(vals[k]["FETCH_SIZE"]) / len(vals[k]["FETCH_SIZE"])
+            # only the fused feature-major scorer takes several batches a dispatch
+            g = per if k.startswith("k_score_fm") and k.rstrip(">").endswith(("1", "true")) else 1
+            rd = 2048 * sum(vals[k]["FETCH_SIZE"]) / len(vals[k]["FETCH_SIZE"]) / g
             wr = vals[k].get("WRITE_SIZE")
-            wrb = 1024 * sum(wr) / len(wr) if wr else 0.0
+            wrb = 1024 * sum(wr) / len(wr) / g if wr else 0.0
             ent = {"hbm_bytes_per_launch": rd + wrb, "read_bytes": rd, "write_bytes": wrb,
-                   "source": os.path.normpath(root), "kernel_build_id": bid}
+                   "source": os.path.normpath(root), "kernel_build_id": bid, "batches_per_dispatch": g}
             if k in avg:
-                ent["rocprof_avg_ms"] = avg[k]
+                ent["rocprof_avg_ms"] = avg[k] / g
             # VALU view (bench.py "valu", "roofline.valu_issue"): instructions
             # issued per class, active VALU quad-cycles, waits -- every SQ_
             # counter collected for this kernel (mean per launch)
             for c in sorted(vals[k]):
                 if c.startswith("SQ_"):
-                    ent[c] = sum(vals[k][c]) / len(vals[k][c])
+                    ent[c] = sum(vals[k][c]) / len(vals[k][c]) / g
             table[f"{k}@{slots}"] = ent
         with open(traffic_json, "w") as f:
             json.dump(table, f, indent=1, sort_keys=True)
@@ -105,5 +114,6 @@ if __name__ == "__main__":
     ap.add_argument("--slots", type=int)
     ap.add_argument("--traffic-json")
     ap.add_argument("--stats")
+    ap.add_argument("--batches-per-dispatch", type=int, default=1)
     a = ap.parse_args()
-    main(a.root, a.slots, a.traffic_json, a.stats)
+    main(a.root, a.slots, a.traffic_json, a.stats, max(1, a.batches_per_dispatch))
