@@ -331,6 +331,10 @@ struct Workspace {
     DevBuf<uint32_t> cs_arrive[2];
     hipEvent_t sum_done[2] = {nullptr, nullptr}, sum_k0[2] = {nullptr, nullptr}, sum_k1[2] = {nullptr, nullptr};
     bool spec_pending[2] = {false, false};   // a speculative chunk of this set may still run
+    // guided sampling: the problem's CDF (N) followed by its coarse table
+    // (guided.h).  A speculative chunk's generator may still read it, so it
+    // lives as long as the chunk buffers and is rewritten only behind await_spec.
+    DevBuf<double> guided_tab;
     // score_models' completion flags (ScoreOut::done): the small scorer stores
     // done_epoch into lo_done[m] after model m's results; the results, list
     // bits and flags live in coherent pinned memory, so the host waits on the
@@ -559,6 +563,19 @@ struct gcr_problem {
     std::unique_ptr<Workspace> own;     // gcr_problem_create: private buffers
     Workspace* w = nullptr;             // own.get() or &ctx->shared
     bool scales_ok = true;              // exact.h scales_in_range over the scale features
+    // guided sampling (guided.h, gcr_problem_set_probabilities): the CDF and
+    // its coarse table in the workspace's guided_tab; gt.cdf == nullptr:
+    // uniform.  Handed to the generator launches only.
+    GuidedTable gt{};
+    // GCR_GUIDED_FLAT=1 (read per launch; A/B of the two-level search): the
+    // same CDF as ONE bucket -- its coarse table is the CDF's last entry --
+    // so every draw is a flat binary search over global memory
+    GuidedTable gt_flat{};
+    const GuidedTable* guided() const {
+        if (!gt.cdf) return nullptr;
+        const char* e = getenv("GCR_GUIDED_FLAT");
+        return (e && e[0] == '1') ? &gt_flat : &gt;
+    }
 };
 
 namespace {
@@ -1560,7 +1577,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static bool valid(int, const Model&) { return true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
-        return launch_generate_geo(P->dp, seed, s0, n, inc, m, s);
+        return launch_generate_geo(P->dp, seed, s0, n, inc, m, s, P->guided());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1619,7 +1636,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     }
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
-        hipError_t e = launch_generate_geo(P->dp, seed, s0, n, b.inc, b.models, s);
+        hipError_t e = launch_generate_geo(P->dp, seed, s0, n, b.inc, b.models, s, P->guided());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -4054,6 +4071,74 @@ int check_params(const gcr_params* p, int solver) {
 void fill_stats(gcr_stats* out, const gcr_stats& st) {
     if (out) *out = st;
 }
+
+// guided.h's table from raw weights: checks them (m: the minimal sample size),
+// then tab = the CDF (n entries, summed sequentially in index order) followed
+// by its coarse table; t describes it with pointers into tab.
+int build_guided(const double* w, size_t n, size_t m, std::vector<double>& tab, GuidedTable& t) {
+    if (!w) return set_err(GCR_EINVAL, "null probabilities");
+    if (n == 0 || n > 0xffffffffull) return set_err(GCR_EINVAL, "probabilities: bad length %zu", n);
+    const uint32_t S = guided_stride((uint32_t)n), B = guided_buckets((uint32_t)n);
+    tab.resize(n + B);
+    double c = 0.0;
+    size_t positive = 0;
+    for (size_t i = 0; i < n; ++i) {
+        const double wi = w[i];
+        if (!(wi >= 0.0) || !std::isfinite(wi))
+            return set_err(GCR_EINVAL, "probabilities must be finite and >= 0 (entry %zu is %g)", i, wi);
+        c = c + wi;
+        if (!std::isfinite(c))
+            return set_err(GCR_EINVAL, "the sum of the probabilities is not finite (at entry %zu)", i);
+        tab[i] = c;
+        positive += wi > 0.0 ? 1 : 0;
+    }
+    if (positive < m)
+        return set_err(GCR_EINVAL, "guided sampling needs at least %zu probabilities > 0, got %zu", m, positive);
+    for (uint32_t k = 0; k < B; ++k) tab[n + k] = tab[std::min<size_t>((size_t)(k + 1) * S, n) - 1];
+    t.cdf = tab.data();
+    t.coarse = tab.data() + n;
+    t.n = (uint32_t)n;
+    t.stride = S;
+    t.buckets = B;
+    t.total = c;
+    return GCR_OK;
+}
+
+size_t minimal_size(int solver) { return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : 3; }
+
+// gcr_problem_set_probabilities.  A speculative chunk still in flight was
+// generated under the previous sampler and reads the previous table: it is
+// awaited first (no run ever consumes a chunk of an earlier run, so waiting
+// for it discards it), then the table is replaced.
+int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
+    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
+        return set_err(GCR_EINVAL, "guided sampling: homography and fundamental-matrix problems only");
+    std::vector<double> tab;
+    GuidedTable t{};
+    if (w != nullptr) {
+        if (n != prob->hc[0].n)
+            return set_err(GCR_EINVAL, "probabilities: length %zu, the problem has %zu correspondences", n,
+                           prob->hc[0].n);
+        if (int e = build_guided(w, n, minimal_size(prob->solver), tab, t)) return e;
+    }
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        HIPC(hipStreamSynchronize(prob->ctx->side));
+        HIPC(hipStreamSynchronize(prob->ctx->stream));
+        prob->gt = prob->gt_flat = GuidedTable{};
+        if (w == nullptr) return GCR_OK;
+        prob->w->guided_tab.ensure(tab.size());
+        HIPC(hipMemcpy(prob->w->guided_tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+        t.cdf = prob->w->guided_tab.p;
+        t.coarse = prob->w->guided_tab.p + n;
+        prob->gt = prob->gt_flat = t;
+        prob->gt_flat.coarse = t.cdf + (n - 1);
+        prob->gt_flat.stride = t.n;
+        prob->gt_flat.buckets = 1;
+        return GCR_OK;
+    });
+}
 }  // namespace
 
 // The batch entry point's solving contexts (a stream pair and a workspace
@@ -4167,6 +4252,11 @@ void gcr_problem_destroy(gcr_problem* prob) {
         try { await_spec(prob->own.get()); } catch (...) {}
     }
     delete prob;
+}
+
+int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities, size_t n) {
+    if (!prob) return set_err(GCR_EINVAL, "null problem");
+    return set_probabilities(prob, probabilities, n);
 }
 
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
@@ -4323,15 +4413,16 @@ int gcr_problem_verify_batch(gcr_problem* prob, const gcr_params* params, uint64
 
 static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                        const gcr_params* params, uint8_t* m0, uint8_t* m1, double* H, gcr_rect_model* model,
-                       gcr_stats* stats) {
+                       gcr_stats* stats, const double* probabilities = nullptr) {
     if (!ctx) return set_err(GCR_EINVAL, "null context");
     if (int e = check_params(params, solver)) return e;
     const auto t0 = Clock::now();
     gcr_problem* prob = nullptr;
     int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true); });
     if (rc != GCR_OK) return rc;
+    if (probabilities != nullptr) rc = set_probabilities(prob, probabilities, n0);
     const double setup = ms_since(t0);
-    rc = gcr_problem_run(prob, params, m0, m1, H, model, stats);
+    if (rc == GCR_OK) rc = gcr_problem_run(prob, params, m0, m1, H, model, stats);
     gcr_problem_destroy(prob);
     if (stats) {
         stats->ms_setup = setup;
@@ -4450,6 +4541,19 @@ int gcr_find_fundamental_matrix(gcr_ctx* ctx, const double* correspondences, siz
                        nullptr, stats_out);
 }
 
+int gcr_find_homography_guided(gcr_ctx* ctx, const double* correspondences, size_t n, const double* probabilities,
+                               const gcr_params* params, uint8_t* mask_out, double* H_out, gcr_stats* stats_out) {
+    return run_oneshot(ctx, GCR_SOLVER_HOMOGRAPHY4, correspondences, n, nullptr, 0, params, mask_out, nullptr, H_out,
+                       nullptr, stats_out, probabilities);
+}
+
+int gcr_find_fundamental_matrix_guided(gcr_ctx* ctx, const double* correspondences, size_t n,
+                                       const double* probabilities, const gcr_params* params, uint8_t* mask_out,
+                                       double* F_out, gcr_stats* stats_out) {
+    return run_oneshot(ctx, GCR_SOLVER_FUNDAMENTAL7, correspondences, n, nullptr, 0, params, mask_out, nullptr, F_out,
+                       nullptr, stats_out, probabilities);
+}
+
 int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* F_out) {
     if (!correspondences || !idx || !F_out) return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
@@ -4478,12 +4582,95 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->inc.ensure(nh);
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_generate_geo(prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s));
+        HIPC(launch_generate_geo(prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
         return GCR_OK;
     });
+}
+
+int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
+                       uint32_t* idx_out) {
+    if (!prob || !idx_out) return set_err(GCR_EINVAL, "null argument");
+    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        const size_t cnt = (size_t)nslots * minimal_size(prob->solver);
+        DevBuf<uint32_t> out;
+        out.ensure(std::max<size_t>(cnt, 1));
+        hipStream_t s = prob->ctx->stream;
+        HIPC(launch_debug_sample(prob->dp, seed, slot0, nslots, attempt, out.p, s, prob->guided()));
+        HIPC(hipMemcpyAsync(idx_out, out.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        return GCR_OK;
+    });
+}
+
+int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, int reps,
+                           double* ms_out) {
+    if (!prob || !ms_out || reps < 1 || nslots == 0) return set_err(GCR_EINVAL, "invalid argument");
+    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        const size_t nh = (size_t)nslots * GeoTraits::per(prob);
+        prob->w->inc.ensure(nh);
+        prob->w->gmodels.ensure(nh);
+        hipStream_t s = prob->ctx->stream;
+        // one untimed launch first (code object load, caches)
+        HIPC(launch_generate_geo(prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
+        HIPC(hipEventRecord(prob->ctx->ev0, s));
+        for (int r = 0; r < reps; ++r)
+            HIPC(launch_generate_geo(prob->dp, seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
+                                     prob->w->gmodels.p, s, prob->guided()));
+        HIPC(hipEventRecord(prob->ctx->ev1, s));
+        HIPC(hipEventSynchronize(prob->ctx->ev1));
+        float ms = 0.f;
+        HIPC(hipEventElapsedTime(&ms, prob->ctx->ev0, prob->ctx->ev1));
+        *ms_out = (double)ms / reps;
+        return GCR_OK;
+    });
+}
+
+int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, const uint32_t* idx,
+                           double* models_out, uint32_t* count_out) {
+    if (!correspondences || !idx || !models_out || !count_out) return set_err(GCR_EINVAL, "null argument");
+    if (solver != GCR_SOLVER_HOMOGRAPHY4 && solver != GCR_SOLVER_FUNDAMENTAL7)
+        return set_err(GCR_EINVAL, "gcr_host_solve_minimal: homography or fundamental matrix");
+    const int m = (int)minimal_size(solver);
+    double x1[7], y1[7], x2[7], y2[7];
+    for (int j = 0; j < m; ++j) {
+        if (idx[j] >= n) return set_err(GCR_EINVAL, "index out of range");
+        const double* r = correspondences + 4 * (size_t)idx[j];
+        x1[j] = r[0];
+        y1[j] = r[1];
+        x2[j] = r[2];
+        y2[j] = r[3];
+    }
+    *count_out = 0;
+    if (solver == GCR_SOLVER_HOMOGRAPHY4) {
+        // kernels.hip attempt<3>
+        GeoModel g = default_geo();
+        if (!valid_sample_h4(x1, y1, x2, y2) || !solve_h4(x1, y1, x2, y2, g)) return GCR_OK;
+        for (int q = 0; q < 9; ++q) models_out[q] = g.h[q];
+        *count_out = 1;
+        return GCR_OK;
+    }
+    // kernels.hip attempt_f and the winning lane's models
+    F7Basis b;
+    if (solve_f7_basis(x1, y1, x2, y2, b) == 0) return GCR_OK;
+    uint32_t k = 0;
+    for (int q = 0; q < 3; ++q)
+        if (b.valid & (1u << q)) {
+            f7_model(b, f7_root(b, q), models_out + 9 * k);
+            ++k;
+        }
+    *count_out = k;
+    return GCR_OK;
 }
 
 int gcr_debug_score_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels, uint32_t* n0,
@@ -4763,6 +4950,23 @@ int gcr_host_sample(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream
     if (!out || m > 32) return set_err(GCR_EINVAL, "bad sample request");
     WordStream ws(seed, index, sub, stream, cls);
     return sample_distinct<32>(ws, n, (int)m, out) ? GCR_OK : set_err(GCR_EINTERNAL, "sample budget exhausted");
+}
+
+int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m) {
+    std::vector<double> tab;
+    GuidedTable t{};
+    return build_guided(probabilities, n, m, tab, t);
+}
+
+int gcr_host_sample_guided(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls,
+                           const double* probabilities, size_t n, uint32_t m, uint32_t* out) {
+    if (!out || m == 0 || m > 32) return set_err(GCR_EINVAL, "bad sample request");
+    std::vector<double> tab;
+    GuidedTable t{};
+    if (int e = build_guided(probabilities, n, m, tab, t)) return e;
+    WordStream ws(seed, index, sub, stream, cls);
+    return sample_guided<32>(ws, t, t.coarse, (int)m, out) ? GCR_OK
+                                                            : set_err(GCR_EINTERNAL, "sample budget exhausted");
 }
 
 int gcr_debug_math(gcr_ctx* ctx, int op, const double* a, const double* b, size_t n, double* out) {

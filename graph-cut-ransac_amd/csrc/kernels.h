@@ -8,6 +8,7 @@
 #include "fund.h"
 #include "geo.h"
 #include "gram.h"
+#include "guided.h"
 #include "rect.h"
 #include "summary.h"
 
@@ -286,8 +287,15 @@ bool verify_chains(uint32_t nslots);
 // solver 3 (homography): one hypothesis per slot; solver 4 (fundamental
 // matrix): kFModels hypotheses per slot (inc / models sized kFModels * nslots,
 // see k_generate_f).  Score / mask / select dispatch on the same solver.
+// guided != nullptr: samples are drawn with the table's probabilities
+// (guided.h) by the generators' guided instantiations; the table goes to the
+// generator launches alone, DevProblem does not carry it.
 hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
-                               GeoModel* models, hipStream_t stream);
+                               GeoModel* models, hipStream_t stream, const GuidedTable* guided = nullptr);
+// The generators' sampling function alone (tests): the 4 / 7 indices of
+// attempt `attempt` of each slot into out, all-ones where the draw budget ran out.
+hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
+                               uint32_t* out, hipStream_t stream, const GuidedTable* guided = nullptr);
 // Hypotheses per workgroup of the batch scorers at a launch of nh (64, 16 or
 // 4; GCR_SPLIT_H pins one for sweeps).
 int split_h(uint32_t nh);

@@ -15,6 +15,7 @@
 // the host restatement.
 #include "kernels.h"
 #include "fm_groups.h"
+#include "guided.h"
 #include "philox.h"
 #include "qr3.h"
 
@@ -35,18 +36,47 @@ constexpr int kScoreBlock = 256;
 constexpr int kMaskBlock = 256;
 
 // ------------------------------------------------------------- generate ----
+// How the correspondence estimators' attempts draw their sample: uniformly
+// (philox.h sample_distinct) or guided by the problem's probabilities
+// (guided.h), the coarse table read from the workgroup's LDS copy.
+struct UniformDraw {};
+struct GuidedDraw {
+    GuidedTable t;
+    const double* coarse;               // LDS (stage_draw)
+};
+
+template <int M, class DRAW>
+GCR_DEVICE bool draw_sample(WordStream& ws, uint64_t n, const DRAW& d, uint32_t* idx) {
+    if constexpr (std::is_same_v<DRAW, GuidedDraw>) return sample_guided<M>(ws, d.t, d.coarse, M, idx);
+    else return sample_distinct<M>(ws, n, M, idx);
+}
+
+// A generator kernel's trailing arguments are nothing (uniform draws: the
+// kernel is the one it was without guided sampling) or one GuidedTable.  Then
+// the workgroup copies the coarse table to LDS once; every thread of the
+// workgroup calls this before anything else, so all waves reach the barrier
+// (the widening generator's lanes change slots between rounds: the copy
+// belongs to the workgroup, not to a slot).
+GCR_DEVICE UniformDraw stage_draw() { return UniformDraw{}; }
+GCR_DEVICE GuidedDraw stage_draw(const GuidedTable& t) {
+    __shared__ double s_coarse[kGuidedCoarse];
+    for (uint32_t i = threadIdx.x; i < t.buckets && i < kGuidedCoarse; i += blockDim.x) s_coarse[i] = t.coarse[i];
+    __syncthreads();
+    return GuidedDraw{t, s_coarse};
+}
+
 // One attempt of one outer-iteration slot: Philox sample -> sample validity ->
 // minimal solve.  Attempts of a slot are independent draws (the counter RNG is
 // keyed by (slot, attempt)), so they may be evaluated in any order/parallel.
-template <int KIND>
+template <int KIND, class DRAW = UniformDraw>
 GCR_DEVICE bool attempt(const DevProblem& p, uint64_t seed, uint64_t slot, uint32_t a,
-                        typename ModelOf<KIND>::type& m) {
+                        typename ModelOf<KIND>::type& m, const DRAW& dr = DRAW{}) {
     if constexpr (KIND == 3) {
         // homography: 4 correspondences, orientation check, 4-point DLT (geo.h)
         const DevClass& c = p.cls[0];
         uint32_t idx[4];
         WordStream ws(seed, slot, a, kStreamMain, 0);
-        if (!sample_distinct<4>(ws, c.n, 4, idx)) return false;
+        if (!draw_sample<4>(ws, c.n, dr, idx)) return false;
         double x1[4], y1[4], x2[4], y2[4];
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -100,11 +130,13 @@ GCR_DEVICE bool attempt(const DevProblem& p, uint64_t seed, uint64_t slot, uint3
 // attempts r*G .. r*G+G-1 in parallel; the slot's result is the lowest
 // successful attempt, exactly the first success of the reference's sequential
 // retry loop (GCRANSAC.h:296-339).  inc = attempt + 1, or 102 if all 101 fail.
-template <int KIND, int G>
+template <int KIND, int G, class... GT>
 __global__ __launch_bounds__(kGenBlock) void k_generate(DevProblem p, uint64_t seed, uint64_t slot0,
                                                         uint32_t nslots, uint8_t* __restrict__ inc,
-                                                        typename ModelOf<KIND>::type* __restrict__ models) {
+                                                        typename ModelOf<KIND>::type* __restrict__ models,
+                                                        GT... gt) {
     static_assert(G >= 1 && G <= 64 && (64 % G) == 0, "group size");
+    const auto dr = stage_draw(gt...);
     const uint32_t tid = blockIdx.x * kGenBlock + threadIdx.x;
     const uint32_t s = tid / G;
     const uint32_t g = tid % G;
@@ -115,7 +147,7 @@ __global__ __launch_bounds__(kGenBlock) void k_generate(DevProblem p, uint64_t s
     for (uint32_t r = 0; r * G < 101; ++r) {
         const uint32_t a = r * G + g;
         typename ModelOf<KIND>::type m = ModelOf<KIND>::def();
-        const bool ok = a < 101 && attempt<KIND>(p, seed, slot, a, m);
+        const bool ok = a < 101 && attempt<KIND>(p, seed, slot, a, m, dr);
         const uint64_t mask = __ballot(ok);
         const uint64_t grp = G == 64 ? mask : (mask >> gbase) & ((1ull << G) - 1ull);
         if (grp) {
@@ -135,11 +167,13 @@ __global__ __launch_bounds__(kGenBlock) void k_generate(DevProblem p, uint64_t s
 // Fundamental matrix: one attempt = Philox sample of 7 correspondences ->
 // 7-point solver (fund.h) into a register-resident basis; 0..3 models.  No
 // sample-validity test beyond the solver's own rank and orientation checks.
-GCR_DEVICE int attempt_f(const DevProblem& p, uint64_t seed, uint64_t slot, uint32_t a, F7Basis& b) {
+template <class DRAW>
+GCR_DEVICE int attempt_f(const DevProblem& p, uint64_t seed, uint64_t slot, uint32_t a, F7Basis& b,
+                         const DRAW& dr) {
     const DevClass& c = p.cls[0];
     uint32_t idx[7];
     WordStream ws(seed, slot, a, kStreamMain, 0);
-    if (!sample_distinct<7>(ws, c.n, 7, idx)) return 0;
+    if (!draw_sample<7>(ws, c.n, dr, idx)) return 0;
     double x1[7], y1[7], x2[7], y2[7];
 #pragma unroll
     for (int j = 0; j < 7; ++j) {
@@ -156,11 +190,12 @@ GCR_DEVICE int attempt_f(const DevProblem& p, uint64_t seed, uint64_t slot, uint
 // attempts failed); inc[3s + k], k >= 1, = 0 if the k-th model exists (scored,
 // no extra iterations) and 255 if not (skipped).  The winning lane rebuilds
 // its models from the basis and writes them straight to global memory.
-template <int G>
+template <int G, class... GT>
 __global__ __launch_bounds__(kGenBlock) void k_generate_f(DevProblem p, uint64_t seed, uint64_t slot0,
                                                           uint32_t nslots, uint8_t* __restrict__ inc,
-                                                          GeoModel* __restrict__ models) {
+                                                          GeoModel* __restrict__ models, GT... gt) {
     static_assert(G >= 1 && G <= 64 && (64 % G) == 0, "group size");
+    const auto dr = stage_draw(gt...);
     const uint32_t tid = blockIdx.x * kGenBlock + threadIdx.x;
     const uint32_t s = tid / G;
     const uint32_t g = tid % G;
@@ -171,7 +206,7 @@ __global__ __launch_bounds__(kGenBlock) void k_generate_f(DevProblem p, uint64_t
     for (uint32_t r = 0; r * G < 101; ++r) {
         const uint32_t a = r * G + g;
         F7Basis b;
-        const int cnt = a < 101 ? attempt_f(p, seed, slot, a, b) : 0;
+        const int cnt = a < 101 ? attempt_f(p, seed, slot, a, b, dr) : 0;
         const uint64_t mask = __ballot(cnt > 0);
         const uint64_t grp = G == 64 ? mask : (mask >> gbase) & ((1ull << G) - 1ull);
         if (grp) {
@@ -215,12 +250,14 @@ __global__ __launch_bounds__(kGenBlock) void k_generate_f(DevProblem p, uint64_t
 // average at 80 % outliers, p99 35) then gets the lanes its finished
 // neighbours no longer use, instead of holding the launch for many rounds of
 // G lanes.
-template <int KIND, int G>
+template <int KIND, int G, class... GT>
 __global__ __launch_bounds__(kGenBlock) void k_generate_fw(DevProblem p, uint64_t seed, uint64_t slot0,
                                                            uint32_t nslots, uint8_t* __restrict__ inc,
-                                                           typename ModelOf<KIND>::type* __restrict__ models) {
+                                                           typename ModelOf<KIND>::type* __restrict__ models,
+                                                           GT... gt) {
     constexpr int S = 64 / G;
     static_assert(S >= 1 && S * G == 64, "slots per wave");
+    const auto dr = stage_draw(gt...);  // before the first round
     const int lane = threadIdx.x & 63;
     const uint32_t s0 = (blockIdx.x * kGenBlock + (threadIdx.x & ~63u)) / G;   // the wave's first slot
     const uint32_t live = s0 < nslots ? nslots - s0 : 0;
@@ -244,10 +281,10 @@ __global__ __launch_bounds__(kGenBlock) void k_generate_fw(DevProblem p, uint64_
         std::conditional_t<KIND == 4, F7Basis, typename ModelOf<KIND>::type> b;
         int cnt = 0;
         if constexpr (KIND == 4) {
-            cnt = (si >= 0 && a < 101) ? attempt_f(p, seed, slot0 + s0 + (uint32_t)si, a, b) : 0;
+            cnt = (si >= 0 && a < 101) ? attempt_f(p, seed, slot0 + s0 + (uint32_t)si, a, b, dr) : 0;
         } else {
             b = ModelOf<KIND>::def();
-            cnt = (si >= 0 && a < 101 && attempt<KIND>(p, seed, slot0 + s0 + (uint32_t)si, a, b)) ? 1 : 0;
+            cnt = (si >= 0 && a < 101 && attempt<KIND>(p, seed, slot0 + s0 + (uint32_t)si, a, b, dr)) ? 1 : 0;
         }
         const uint64_t mask = __ballot(cnt > 0);
         nx += 1u << lw;
@@ -5074,8 +5111,11 @@ hipError_t launch_math(int op, const double* a, const double* b, size_t n, doubl
 
 // ------------------------------------ homography (3) / fundamental (4) ----
 hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
-                               GeoModel* models, hipStream_t stream) {
+                               GeoModel* models, hipStream_t stream, const GuidedTable* guided) {
     if (nslots == 0) return hipSuccess;
+    if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
+                              (size_t)guided->stride * guided->buckets < guided->n))
+        return hipErrorInvalidValue;
     // GCR_GEN_WIDEN=0: the fundamental-matrix generator keeps fixed groups of
     // G lanes per slot (k_generate_f) instead of widening them (k_generate_fw).
     // Both knobs are read per launch (tests switch them in-process).
@@ -5087,16 +5127,25 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
     auto go = [&](auto gtag) {
         constexpr int G = decltype(gtag)::value;
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
-        if (p.solver == 4) {
-            if (widen)
-                hipLaunchKernelGGL((k_generate_fw<4, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models);
-            else
-                hipLaunchKernelGGL((k_generate_f<G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models);
-        } else if (hwiden) {
-            hipLaunchKernelGGL((k_generate_fw<3, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models);
-        } else {
-            hipLaunchKernelGGL((k_generate<3, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models);
-        }
+        // t: nothing (the uniform kernels) or the guided table
+        auto run = [&](auto... t) {
+            if (p.solver == 4) {
+                if (widen)
+                    hipLaunchKernelGGL((k_generate_fw<4, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
+                                       nslots, inc, models, t...);
+                else
+                    hipLaunchKernelGGL((k_generate_f<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
+                                       nslots, inc, models, t...);
+            } else if (hwiden) {
+                hipLaunchKernelGGL((k_generate_fw<3, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
+                                   nslots, inc, models, t...);
+            } else {
+                hipLaunchKernelGGL((k_generate<3, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0, nslots,
+                                   inc, models, t...);
+            }
+        };
+        if (guided != nullptr) run(*guided);
+        else run();
     };
     // GCR_GEN_G overrides the lanes per slot (1 .. 64)
     const char* eg = getenv("GCR_GEN_G");
@@ -5121,6 +5170,43 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
         case 2: go(std::integral_constant<int, 2>{}); break;
         default: go(std::integral_constant<int, 1>{}); break;
     }
+    return hipGetLastError();
+}
+
+// The generators' sampling function alone (tests): attempt `a` of each slot,
+// M indices per slot, all-ones where the draw budget ran out.
+template <int M, class... GT>
+__global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t seed, uint64_t slot0,
+                                                            uint32_t nslots, uint32_t a, uint32_t* __restrict__ out,
+                                                            GT... gt) {
+    const auto dr = stage_draw(gt...);
+    const uint32_t s = blockIdx.x * kGenBlock + threadIdx.x;
+    if (s >= nslots) return;
+    uint32_t idx[M];
+    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
+    const bool ok = draw_sample<M>(ws, n, dr, idx);
+#pragma unroll
+    for (int j = 0; j < M; ++j) out[(size_t)M * s + j] = ok ? idx[j] : 0xffffffffu;
+}
+
+hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
+                               uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
+    if (nslots == 0) return hipSuccess;
+    if (p.solver != 3 && p.solver != 4) return hipErrorInvalidValue;
+    if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
+                              (size_t)guided->stride * guided->buckets < guided->n))
+        return hipErrorInvalidValue;
+    const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
+    auto run = [&](auto... t) {
+        if (p.solver == 4)
+            hipLaunchKernelGGL((k_debug_sample<7, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
+                               nslots, attempt, out, t...);
+        else
+            hipLaunchKernelGGL((k_debug_sample<4, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
+                               nslots, attempt, out, t...);
+    };
+    if (guided != nullptr) run(*guided);
+    else run();
     return hipGetLastError();
 }
 

@@ -194,6 +194,17 @@ def _load():
     L.gcr_host_fit_h.argtypes = [dp, C.c_size_t, u32p, C.c_size_t, dp]
     L.gcr_find_fundamental_matrix.argtypes = L.gcr_find_homography.argtypes
     L.gcr_host_fit_f.argtypes = L.gcr_host_fit_h.argtypes
+    # guided (importance) sampling: gcr_problem_set_probabilities, the guided
+    # one-shot entries and their host / debug hooks
+    L.gcr_problem_set_probabilities.argtypes = [vp, vp, C.c_size_t]
+    L.gcr_find_homography_guided.argtypes = [vp, vp, C.c_size_t, vp, C.POINTER(Params), vp, vp, C.POINTER(Stats)]
+    L.gcr_find_fundamental_matrix_guided.argtypes = L.gcr_find_homography_guided.argtypes
+    L.gcr_host_sample_guided.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t,
+                                         C.c_uint32, u32p]
+    L.gcr_host_check_probabilities.argtypes = [vp, C.c_size_t, C.c_uint32]
+    L.gcr_debug_sample_h.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, u32p]
+    L.gcr_measure_generate_h.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, dp]
+    L.gcr_host_solve_minimal.argtypes = [C.c_int, dp, C.c_size_t, u32p, dp, u32p]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

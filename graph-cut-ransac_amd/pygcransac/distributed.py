@@ -234,7 +234,8 @@ class Comm:
 
 
 def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None, rank: int = 0, world: int = 1,
-                        dist=None, device: Optional[int] = None, coll_device=None, comm: Optional[Comm] = None):
+                        dist=None, device: Optional[int] = None, coll_device=None, comm: Optional[Comm] = None,
+                        probabilities=None):
     """One estimator problem over `world` ranks.
 
     Every rank calls this with the same inputs; each verifies its block of
@@ -243,6 +244,9 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     gcr_params fields (scale_residual_thresh, confidence, seed, ...).  With
     `comm` (a Comm) the exchange runs inside the engine (ncclAllGather on the
     device); otherwise through `dist` in a Python callback (gloo or RCCL).
+    `probabilities` (homography / fundamental matrix only; one weight per
+    correspondence) switches the problem to guided sampling
+    (gcr_problem_set_probabilities), the same on every rank.
     Returns (H (3, 3) or None, masks tuple, stats dict, rect model record)."""
     import ctypes as C
 
@@ -256,6 +260,9 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     N.check(N.lib.gcr_problem_create(ctx, solver, dp(f0), f0.shape[0], dp(f1) if f1 is not None else None,
                                      0 if f1 is None else f1.shape[0], C.byref(h)))
     try:
+        if probabilities is not None:
+            w = np.ascontiguousarray(probabilities, dtype=np.float64).reshape(-1)
+            N.check(N.lib.gcr_problem_set_probabilities(h, w.ctypes.data, w.shape[0]))
         p = N.default_params()
         for k, v in (params or {}).items():
             setattr(p, k, v)

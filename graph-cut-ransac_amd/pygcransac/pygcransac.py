@@ -428,15 +428,31 @@ def _set_grid(p, correspondences, h1, w1, h2, w2, neighborhood_size):
         p.cell_size[:] = sizes
 
 
-def _correspondence_call(entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
+def _as_probabilities(probabilities, n, m):
+    """The guided sampler's weights as a contiguous float64 vector of length
+    n, checked by the engine for a minimal sample of m (before any GPU work:
+    a bad vector is a ValueError with the engine's message)."""
+    w = np.ascontiguousarray(np.asarray(probabilities, dtype=np.float64))
+    if w.ndim != 1 or w.shape[0] != n:
+        raise ValueError(f"probabilities must be a vector with one entry per correspondence ({n}); "
+                         f"it has shape {tuple(w.shape)}.")
+    N.check(N.lib.gcr_host_check_probabilities(w.ctypes.data, n, m))
+    return w
+
+
+def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                          spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                          batch_slots, return_stats, min_rows, neighborhood_size):
     for name, v in (("h1", h1), ("w1", w1), ("h2", h2), ("w2", w2)):
         _as_double(v, name)
-    if probabilities is not None and len(probabilities) != 0:
-        raise ValueError("Only the uniform sampler is supported; probabilities must be empty.")
-    if _as_size_t(sampler, "sampler") != 0:
-        raise ValueError(f"Unsupported sampler {sampler}: only 0 (uniform) is supported.")
+    sampler_id = _as_size_t(sampler, "sampler")
+    if sampler_id not in (0, 3):
+        raise ValueError(f"Unsupported sampler {sampler}: only 0 (uniform) and 3 (guided by probabilities, "
+                         f"importance sampling) are supported.")
+    if sampler_id == 0 and probabilities is not None and len(probabilities) != 0:
+        raise ValueError("The uniform sampler (0) takes no probabilities; they must be empty (sampler=3 uses them).")
+    if sampler_id == 3 and probabilities is None:
+        raise ValueError("sampler=3 (guided) needs probabilities, one per correspondence.")
     f = _as_features(correspondences)
     if f.ndim != 2:
         raise ValueError("Number of dimensions must be 2.")
@@ -450,8 +466,13 @@ def _correspondence_call(entry, correspondences, h1, w1, h2, w2, probabilities, 
     mask = np.zeros(n, dtype=np.uint8)
     M = np.zeros(9, dtype=np.float64)
     st = N.Stats()
+    w = _as_probabilities(probabilities, n, min_rows) if sampler_id == 3 else None
     ctx = N.context(device)
-    rc = entry(ctx, f.ctypes.data, n, C.byref(p), mask.ctypes.data, M.ctypes.data, C.byref(st))
+    if sampler_id == 3:
+        rc = guided_entry(ctx, f.ctypes.data, n, w.ctypes.data, C.byref(p), mask.ctypes.data, M.ctypes.data,
+                          C.byref(st))
+    else:
+        rc = entry(ctx, f.ctypes.data, n, C.byref(p), mask.ctypes.data, M.ctypes.data, C.byref(st))
     num_inliers = N.check(rc)
     inliers = mask.view(bool)
     extra = (st.as_dict(),) if return_stats else ()
@@ -473,15 +494,20 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     w2/k, h2/k; a size <= 0 is taken from the data's extent), and
     ``spatial_coherence_weight`` (lambda) weighs its pairwise terms in every
     graph-cut labeling (GCRANSAC.h:759-870); ``neighborhood_size=0`` or
-    lambda = 0 gives the empty grid.  ``sampler`` must be 0 (uniform) and
-    ``probabilities`` empty.  ``threshold`` is the inlier threshold in pixels
+    lambda = 0 gives the empty grid.  ``sampler`` is 0 (uniform, ``probabilities``
+    empty) or 3 (guided, upstream's importance sampler): ``probabilities`` then
+    holds one weight per correspondence (finite, >= 0, at least 4 of them > 0),
+    and every minimal sample of the main loop draws correspondence i with
+    probability w[i] / sum(w); a zero weight is never drawn, and local
+    optimisation's inner sampler stays uniform.  ``threshold`` is the inlier threshold in pixels
     of the second image (MSAC threshold 2.25 * threshold, as the rectification
     solvers).
 
     Returns ``(H, inliers)`` with H (3, 3) and H[2, 2] = 1, or ``(None, inliers)``.
     """
-    return _correspondence_call(N.lib.gcr_find_homography, correspondences, h1, w1, h2, w2, probabilities,
-                                threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
+    return _correspondence_call(N.lib.gcr_find_homography, N.lib.gcr_find_homography_guided, correspondences,
+                                h1, w1, h2, w2, probabilities, threshold, conf, spatial_coherence_weight, max_iters,
+                                min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size)
 
 
@@ -491,11 +517,13 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
     """7-point fundamental matrix with graph-cut LO -- an EXTENSION like
     findHomography (same arguments, the same neighbourhood grid; upstream
     pygcransac's findFundamentalMatrix order).  The residual is the Sampson distance in pixels; a sample yields up
-    to three models, each scored.
+    to three models, each scored.  ``sampler=3`` with ``probabilities`` (at least
+    7 of them > 0) guides the 7-point samples as it does findHomography's.
 
     Returns ``(F, inliers)`` with F (3, 3), unit Frobenius norm and
     x2^T F x1 = 0, or ``(None, inliers)``.
     """
-    return _correspondence_call(N.lib.gcr_find_fundamental_matrix, correspondences, h1, w1, h2, w2, probabilities,
+    return _correspondence_call(N.lib.gcr_find_fundamental_matrix, N.lib.gcr_find_fundamental_matrix_guided,
+                                correspondences, h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 7, neighborhood_size)

@@ -35,6 +35,9 @@
 extern "C" {
 #endif
 
+/* Guided sampling (gcr_problem_set_probabilities, the *_guided entries and
+ * their debug hooks) was added without a version change: every addition is a
+ * new function, no struct changed size or layout, so the version stays 5. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -167,6 +170,21 @@ int gcr_find_homography(gcr_ctx* ctx, const double* correspondences, size_t n, c
 int gcr_find_fundamental_matrix(gcr_ctx* ctx, const double* correspondences, size_t n, const gcr_params* params,
                                 uint8_t* mask_out, double* F_out, gcr_stats* stats_out);
 
+/* Guided (importance) sampling, upstream GC-RANSAC's sampler 3: the one-shot
+ * entries above with per-correspondence sampling weights, `probabilities`
+ * (n float64, each finite and >= 0, at least 4 / 7 of them > 0, a finite sum;
+ * anything else is GCR_EINVAL).  Every minimal sample of the main loop draws
+ * correspondence i with probability w[i] / sum(w) (csrc/guided.h is the
+ * definition); a zero weight is never drawn.  Validity checks, solvers,
+ * scoring, the adaptive stop and local optimisation (whose inner sampler
+ * stays uniform) are unchanged.  probabilities == NULL: exactly the plain
+ * entry. */
+int gcr_find_homography_guided(gcr_ctx* ctx, const double* correspondences, size_t n, const double* probabilities,
+                               const gcr_params* params, uint8_t* mask_out, double* H_out, gcr_stats* stats_out);
+int gcr_find_fundamental_matrix_guided(gcr_ctx* ctx, const double* correspondences, size_t n,
+                                       const double* probabilities, const gcr_params* params, uint8_t* mask_out,
+                                       double* F_out, gcr_stats* stats_out);
+
 /* ---- batches of independent problems (SURVEY.md §8(b) gcr_rect_batch,
  * BASELINE configs[4]) ----------------------------------------------------- */
 typedef struct gcr_batch_item {
@@ -198,6 +216,15 @@ int gcr_solve_batch(int device, gcr_batch_item* items, size_t n, int concurrency
 int gcr_problem_create(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                        gcr_problem** out);
 void gcr_problem_destroy(gcr_problem* prob);
+/* Guided sampling for a resident homography / fundamental-matrix problem (see
+ * gcr_find_homography_guided): n must be the problem's N.  Everything that
+ * generates from the problem afterwards -- gcr_problem_run, _run_sharded,
+ * _run_comm, _verify_batch(es), gcr_debug_generate_h -- draws its samples
+ * with these weights.  probabilities == NULL (n ignored) returns the problem
+ * to uniform sampling.  Either call first waits for a speculative chunk a
+ * previous run left in flight.  Rectification problems: GCR_EINVAL.
+ * gcr_solve_batch's items carry no probabilities and stay uniform. */
+int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities, size_t n);
 /* full estimator call on the resident problem (same semantics as gcr_rect_*) */
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
                     double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out);
@@ -304,6 +331,23 @@ int gcr_host_fit_nonminimal(int solver, const double* f0, size_t n0, const doubl
  * 2.25 thr); mask: rules as gcr_debug_mask */
 int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc_out,
                          double* H_out);
+/* the generators' sampling function alone: the 4 / 7 indices of attempt
+ * `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out: 4 / 7 per slot,
+ * all-ones where the draw budget ran out), with the problem's sampler --
+ * guided after gcr_problem_set_probabilities, else uniform */
+int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
+                       uint32_t* idx_out);
+/* measurement (tools/guided_bench.py): HIP-event time per launch, in ms, of
+ * `reps` back-to-back generator launches of nslots slots each (consecutive
+ * slot ranges from slot0) with the problem's sampler, after one untimed launch */
+int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, int reps,
+                           double* ms_out);
+/* host-only: the generators' validity check + minimal solver on the listed
+ * rows (4: valid_sample_h4 + solve_h4; 7: solve_f7_basis + f7_model), in list
+ * order, the functions the kernels call.  *count_out = 0 .. 3 models, 9
+ * doubles each in models_out (room for 27). */
+int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, const uint32_t* idx,
+                           double* models_out, uint32_t* count_out);
 int gcr_debug_score_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels, uint32_t* n0,
                       double* v0, double* tot);
 int gcr_debug_mask_h(gcr_problem* prob, const gcr_params* params, const double* H, int rule, uint8_t* mask_out);
@@ -349,6 +393,14 @@ double gcr_host_atan2(double y, double x);
 double gcr_host_math(int op, double a, double b);
 int gcr_host_sample(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls, uint64_t n,
                     uint32_t m, uint32_t* out);
+/* host-only: the check gcr_problem_set_probabilities makes of its weights for
+ * a minimal sample of m (GCR_OK, or GCR_EINVAL with a message) */
+int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m);
+/* host-only: one guided sample (csrc/guided.h) from raw weights: m <= 32
+ * distinct indices in draw order; the weights are checked as
+ * gcr_problem_set_probabilities checks them, with m as the minimal size */
+int gcr_host_sample_guided(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls,
+                           const double* probabilities, size_t n, uint32_t m, uint32_t* out);
 /* device evaluation of the same primitives over arrays (GPU parity tests):
  * op 0 log(a), 1 pow_m3(a), 2 atan2(a, b), 3 a / b, 4 sqrt(a),
  * 5 clip_angle_small(a), 6 clip_angle(a), 8 round 3's log (dm_log_fd),
