@@ -51,6 +51,7 @@
 
 #include "gcr.h"
 #include "host_fit.h"
+#include "guided_stop.h"
 #include "kernels.h"
 #include "fm_groups.h"
 #include "philox.h"
@@ -334,7 +335,18 @@ struct Workspace {
     // guided sampling: the problem's CDF (N) followed by its coarse table
     // (guided.h).  A speculative chunk's generator may still read it, so it
     // lives as long as the chunk buffers and is rewritten only behind await_spec.
+    // Behind the coarse table, in the same upload: the weights' N quanta
+    // (guided_stop.h; uint64_t bit patterns), which a run's mass launches read
+    // on the replay stream -- the same lifetime rule.
     DevBuf<double> guided_tab;
+    // the guided stop's mass launches (RunnerT::inlier_masses): the models in
+    // pinned memory and on the device, each model's (count, mass) pinned
+    PinBuf<GeoModel> gm_hmodels;
+    DevBuf<GeoModel> gm_models;
+    DevBuf<uint32_t> gm_dcount;
+    DevBuf<uint64_t> gm_dmass;
+    PinBuf<uint32_t> gm_count;
+    PinBuf<uint64_t> gm_mass;
     // score_models' completion flags (ScoreOut::done): the small scorer stores
     // done_epoch into lo_done[m] after model m's results; the results, list
     // bits and flags live in coherent pinned memory, so the host waits on the
@@ -571,6 +583,10 @@ struct gcr_problem {
     // same CDF as ONE bucket -- its coarse table is the CDF's last entry --
     // so every draw is a flat binary search over global memory
     GuidedTable gt_flat{};
+    // the weights' quanta (guided_stop.h) behind the coarse table in
+    // guided_tab and their sum; set and cleared with gt
+    const uint64_t* gq = nullptr;
+    uint64_t gQ = 0;
     const GuidedTable* guided() const {
         if (!gt.cdf) return nullptr;
         const char* e = getenv("GCR_GUIDED_FLAT");
@@ -1763,6 +1779,7 @@ public:
         N_[1] = K_ == 2 ? P->hc[1].n : 0;
         log_prob_ = std::log(1.0 - prm.confidence);
         do_lo_ = (prm.flags & GCR_FLAG_NO_LO) == 0;
+        gstop_ = (prm.flags & GCR_FLAG_GUIDED_STOP) != 0;      // the entries checked it (check_guided_stop)
         std::memset(&st_, 0, sizeof(st_));
         if (kRect && exact_) {
             sbnd_ = score_bound(Tm_, K_);
@@ -1893,14 +1910,15 @@ public:
                     bool nonmin = false;
                     for (int c = 0; c < K_; ++c) if (best_.n[c] > m_[c]) { nonmin = true; break; }
                     do_lo = (it_ > 20) && nonmin;
-                    max_iteration = iteration_number(best_.n);
+                    if (gstop_) remass_best();          // this replay has no chain: one launch per new best
+                    max_iteration = stop_number();
                 }
             }
             if (do_lo_ && do_lo) {
                 replay_ms += ms_since(t_rep);
                 ++lo_number_;
-                local_optimization(bufs_[off_]);
-                max_iteration = iteration_number(best_.n);
+                if (local_optimization(bufs_[off_]) && gstop_) remass_best();
+                max_iteration = stop_number();
                 t_rep = Clock::now();
             }
             // past the chunk's last possible new best (and its LO): the rest
@@ -2200,6 +2218,10 @@ public:
         std::vector<SumHyp> lasts(world_);
         std::vector<uint8_t> has_last(world_);
         std::vector<uint64_t> itb(world_ + 1), hb(world_ + 1), tgt(world_);
+        // guided stop: (count, mass) of S[r].cand[k] in cand_mass[r][k]
+        std::vector<Model> cand_models;
+        std::vector<MassRec> cand_flat;
+        std::vector<std::vector<MassRec>> cand_mass(world_);
         // plan + issue the chunk after the last issued one; `it_lo`: iterations
         // before it (exact, or a lower bound: every slot adds at least one)
         const bool spec_ok = ahead_ok && speculate_on() && min_it < max_it && prm_.batch_slots == 0;
@@ -2249,6 +2271,21 @@ public:
             // the LO masks for 60-80 us).  LO rarely raises the threshold
             // again; if it does, the next chunk is issued after the replay.
             // Results are identical either way.
+            // guided stop: the masses of every rank's chain members in one
+            // launch, before the walk (every rank holds all features and all
+            // members' models: each computes them locally and identically)
+            if (gstop_) {
+                cand_models.clear();
+                for (int r = 0; r < world_; ++r)
+                    for (uint32_t k = 0; k < S[r].ncand; ++k) cand_models.push_back(model_of(S[r].cand[k]));
+                cand_flat.resize(cand_models.size());
+                inlier_masses(cand_models.data(), (uint32_t)cand_models.size(), cand_flat.data());
+                size_t at = 0;
+                for (int r = 0; r < world_; ++r) {
+                    cand_mass[r].assign(cand_flat.begin() + at, cand_flat.begin() + at + S[r].ncand);
+                    at += S[r].ncand;
+                }
+            }
             uint64_t spec_thr = thr();
             if (spec_ok && spec_trim_on())
                 for (int r = 0; r < world_; ++r)
@@ -2257,7 +2294,9 @@ public:
                         const uint32_t rn[2] = {h.n0, h.n1};
                         const HScore sc = finish(rn, h.v0, h.v1, h.tot);
                         if (best_.sum < sc.sum)
-                            spec_thr = std::min(spec_thr, std::max(min_it, iteration_number(sc.n)));
+                            spec_thr = std::min(
+                                spec_thr, std::max(min_it, gstop_ ? guided_number(cand_mass[r][S[r].ncand - 1].mass)
+                                                                  : iteration_number(sc.n)));
                     }
             if (ahead_ok && q.size() == 1 && (itb[world_] < min_it || (spec_ok && itb[world_] < spec_thr)) &&
                 issue(itb[world_], true))
@@ -2273,8 +2312,8 @@ public:
                 if (do_lo_ && slot_lo) {
                     const auto t_lo = Clock::now();
                     ++lo_number_;
-                    local_optimization(bufs_[off_]);
-                    max_iteration = iteration_number(best_.n);
+                    if (local_optimization(bufs_[off_]) && gstop_) remass_best();
+                    max_iteration = stop_number();
                     lo_ms += ms_since(t_lo);
                 }
                 slot_lo = false;
@@ -2288,6 +2327,12 @@ public:
                         // continues the chain from the last one (collective)
                         resummarise(c, r, S[r].resume_pos, S[r].resume_bar, nullptr, X.data());
                         S[r] = X[r];
+                        if (gstop_) {                       // the continued chain's members: their own launch
+                            cand_models.clear();
+                            for (uint32_t q2 = 0; q2 < S[r].ncand; ++q2) cand_models.push_back(model_of(S[r].cand[q2]));
+                            cand_mass[r].resize(S[r].ncand);
+                            inlier_masses(cand_models.data(), S[r].ncand, cand_mass[r].data());
+                        }
                         k = 0;
                         continue;
                     }
@@ -2330,7 +2375,11 @@ public:
                         bool nonmin = false;
                         for (int cc = 0; cc < K_; ++cc) if (best_.n[cc] > m_[cc]) { nonmin = true; break; }
                         slot_lo = (it_ > 20) && nonmin;
-                        max_iteration = iteration_number(best_.n);
+                        if (gstop_) {
+                            check_mass(cand_mass[r][k - 1], best_.n[0]);
+                            best_mass_ = cand_mass[r][k - 1].mass;
+                        }
+                        max_iteration = stop_number();
                     }
                 }
             }
@@ -3009,6 +3058,74 @@ private:
         if (std::fabs(lg) < std::numeric_limits<double>::epsilon()) return std::numeric_limits<uint64_t>::max();
         return static_cast<uint64_t>(std::ceil(log_prob_ / lg));
     }
+
+    // ---- guided stop (GCR_FLAG_GUIDED_STOP, guided_stop.h) ----------------
+    // max_iteration from the current best's inlier MASS instead of its count.
+    // best_mass_ follows best_: a chain member's mass comes from its chunk's
+    // one launch (replay_summaries), a best found by LO gets a launch of its own.
+    bool gstop_ = false;
+    uint64_t best_mass_ = 0;
+    struct MassRec {
+        uint32_t count;
+        uint64_t mass;
+    };
+    // (count, mass) of nm models: one launch and one synchronisation on the
+    // replay stream
+    void inlier_masses(const Model* models, uint32_t nm, MassRec* out) {
+        if constexpr (!kRect) {
+            if (nm == 0) return;
+            Workspace* w = P_->w;
+            const size_t cap = std::max<size_t>(nm, 64);
+            w->gm_hmodels.ensure(cap);
+            w->gm_count.ensure(cap);
+            w->gm_mass.ensure(cap);
+            std::memcpy(w->gm_hmodels.p, models, (size_t)nm * sizeof(Model));
+            if (zerocopy_on()) {
+                // models read in place, results written straight to pinned memory
+                HIPC(launch_inlier_mass_geo(P_->dp, Tm_[0], dev_view(w->gm_hmodels.p), nm, P_->gq,
+                                            dev_view(w->gm_count.p), dev_view(w->gm_mass.p), s_));
+            } else {
+                w->gm_models.ensure(cap);
+                w->gm_dcount.ensure(cap);
+                w->gm_dmass.ensure(cap);
+                HIPC(hipMemcpyAsync(w->gm_models.p, w->gm_hmodels.p, (size_t)nm * sizeof(Model),
+                                    hipMemcpyHostToDevice, s_));
+                HIPC(launch_inlier_mass_geo(P_->dp, Tm_[0], w->gm_models.p, nm, P_->gq, w->gm_dcount.p,
+                                            w->gm_dmass.p, s_));
+                HIPC(hipMemcpyAsync(w->gm_count.p, w->gm_dcount.p, (size_t)nm * sizeof(uint32_t),
+                                    hipMemcpyDeviceToHost, s_));
+                HIPC(hipMemcpyAsync(w->gm_mass.p, w->gm_dmass.p, (size_t)nm * sizeof(uint64_t),
+                                    hipMemcpyDeviceToHost, s_));
+            }
+            HIPC(hipStreamSynchronize(s_));
+            for (uint32_t k = 0; k < nm; ++k) out[k] = MassRec{w->gm_count.p[k], w->gm_mass.p[k]};
+            st_.launches += 1;
+        } else {
+            (void)models;
+            (void)nm;
+            (void)out;
+            throw std::runtime_error("guided stop: not a correspondence problem");
+        }
+    }
+    // the stop uses the inlier set the score used, or not at all
+    void check_mass(const MassRec& r, uint64_t n0) const {
+        if (r.count != n0)
+            throw std::runtime_error("guided stop: the mass kernel counted " + std::to_string(r.count) +
+                                     " inliers where the scorer counted " + std::to_string(n0));
+        if (r.mass > P_->gQ) throw std::runtime_error("guided stop: an inlier mass above the total");
+    }
+    // the mass of best_ after it changed outside a chunk's chain (LO)
+    void remass_best() {
+        MassRec r{};
+        inlier_masses(&best_val_, 1, &r);
+        check_mass(r, best_.n[0]);
+        best_mass_ = r.mass;
+    }
+    uint64_t guided_number(uint64_t mass) const {
+        return iteration_number_guided(mass, P_->gQ, (uint32_t)m_[0], log_prob_);
+    }
+    // max_iteration of the current best
+    uint64_t stop_number() const { return gstop_ ? guided_number(best_mass_) : iteration_number(best_.n); }
 
     // Generate [s0, s0+B), then score only the slots the loop can still reach
     // (iterations can never pass max(min_it, max_it)).  Returns slots scored.
@@ -4104,7 +4221,34 @@ int build_guided(const double* w, size_t n, size_t m, std::vector<double>& tab, 
     return GCR_OK;
 }
 
+// guided_stop.h's quanta of weights build_guided accepted (total: its
+// t.total); returns their sum Q
+uint64_t build_quanta(const double* w, size_t n, double total, uint64_t* q) {
+    const int K = guided_quanta_shift(n);
+    uint64_t Q = 0;
+    for (size_t i = 0; i < n; ++i) {
+        q[i] = guided_quantum(w[i], total, K);
+        Q += q[i];
+    }
+    return Q;
+}
+
 size_t minimal_size(int solver) { return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : 3; }
+
+// GCR_FLAG_GUIDED_STOP is valid only on a problem that samples guided
+int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
+    if ((params->flags & GCR_FLAG_GUIDED_STOP) == 0) return GCR_OK;
+    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling exists for homography and "
+                                   "fundamental-matrix problems only");
+    if (prob->gt.cdf == nullptr)
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
+                                   "(gcr_problem_set_probabilities)");
+    if (prob->gQ == 0)
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling's weights are too many and too small to "
+                                   "measure (every share is below 2^-%d)", guided_quanta_shift(prob->hc[0].n));
+    return GCR_OK;
+}
 
 // gcr_problem_set_probabilities.  A speculative chunk still in flight was
 // generated under the previous sampler and reads the previous table: it is
@@ -4121,12 +4265,23 @@ int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
                            prob->hc[0].n);
         if (int e = build_guided(w, n, minimal_size(prob->solver), tab, t)) return e;
     }
+    // the quanta behind the table (t's pointers are replaced below)
+    const size_t ntab = tab.size();
+    uint64_t Q = 0;
+    if (w != nullptr) {
+        std::vector<uint64_t> q(n);
+        Q = build_quanta(w, n, t.total, q.data());
+        tab.resize(ntab + n);
+        std::memcpy(tab.data() + ntab, q.data(), n * sizeof(uint64_t));
+    }
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
         HIPC(hipStreamSynchronize(prob->ctx->side));
         HIPC(hipStreamSynchronize(prob->ctx->stream));
         prob->gt = prob->gt_flat = GuidedTable{};
+        prob->gq = nullptr;
+        prob->gQ = 0;
         if (w == nullptr) return GCR_OK;
         prob->w->guided_tab.ensure(tab.size());
         HIPC(hipMemcpy(prob->w->guided_tab.p, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
@@ -4136,6 +4291,9 @@ int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
         prob->gt_flat.coarse = t.cdf + (n - 1);
         prob->gt_flat.stride = t.n;
         prob->gt_flat.buckets = 1;
+        static_assert(sizeof(uint64_t) == sizeof(double), "quanta share guided_tab");
+        prob->gq = reinterpret_cast<const uint64_t*>(prob->w->guided_tab.p + ntab);
+        prob->gQ = Q;
         return GCR_OK;
     });
 }
@@ -4263,6 +4421,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
                     double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out) {
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_guided_stop(prob, params)) return e;
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
@@ -4281,6 +4440,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
                             double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out) {
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_guided_stop(prob, params)) return e;
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allgather))
         return set_err(GCR_EINVAL, "bad rank/world/allgather");
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
@@ -4354,6 +4514,7 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
     if (!prob || !comm) return set_err(GCR_EINVAL, "null problem or communicator");
     if (comm->ctx != prob->ctx) return set_err(GCR_EINVAL, "communicator and problem on different contexts");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_guided_stop(prob, params)) return e;
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
     if (comm->aborted) return set_err(GCR_EINVAL, "communicator was aborted after an earlier error");
     return guard([&]() -> int {
@@ -4392,6 +4553,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
                                uint32_t nbatches, gcr_batch_result* out, gcr_stats* stats_out) {
     if (!prob || !out) return set_err(GCR_EINVAL, "null problem or output");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_guided_stop(prob, params)) return e;
     if (nslots == 0 || nbatches == 0) return set_err(GCR_EINVAL, "nslots and nbatches must be > 0");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
@@ -4416,6 +4578,9 @@ static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, co
                        gcr_stats* stats, const double* probabilities = nullptr) {
     if (!ctx) return set_err(GCR_EINVAL, "null context");
     if (int e = check_params(params, solver)) return e;
+    if ((params->flags & GCR_FLAG_GUIDED_STOP) != 0 && probabilities == nullptr)
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the plain entries and "
+                                   "gcr_solve_batch's items carry no probabilities");
     const auto t0 = Clock::now();
     gcr_problem* prob = nullptr;
     int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true); });
@@ -4726,6 +4891,33 @@ int gcr_debug_mask_h(gcr_problem* prob, const gcr_params* params, const double* 
     });
 }
 
+int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels,
+                            uint32_t* count_out, uint64_t* mass_out) {
+    if (!prob || !params || !H || !count_out || !mass_out) return set_err(GCR_EINVAL, "null argument");
+    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (prob->gq == nullptr)
+        return set_err(GCR_EINVAL, "the inlier mass needs guided sampling: the problem has no probabilities");
+    if (nmodels == 0) return GCR_OK;
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        hipStream_t s = prob->ctx->stream;
+        const double thr = params->scale_residual_thresh;
+        const double T = (2.25 * thr) * thr;
+        Workspace* w = prob->w;
+        w->gm_models.ensure(nmodels);
+        w->gm_dcount.ensure(nmodels);
+        w->gm_dmass.ensure(nmodels);
+        HIPC(hipMemcpyAsync(w->gm_models.p, H, (size_t)nmodels * sizeof(GeoModel), hipMemcpyHostToDevice, s));
+        HIPC(launch_inlier_mass_geo(prob->dp, T, w->gm_models.p, nmodels, prob->gq, w->gm_dcount.p, w->gm_dmass.p, s));
+        HIPC(hipMemcpyAsync(count_out, w->gm_dcount.p, (size_t)nmodels * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(mass_out, w->gm_dmass.p, (size_t)nmodels * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        return GCR_OK;
+    });
+}
+
 int gcr_host_fit_h(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* H_out) {
     if (!correspondences || !idx || !H_out) return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
@@ -4967,6 +5159,25 @@ int gcr_host_sample_guided(uint64_t seed, uint64_t index, uint32_t sub, uint32_t
     WordStream ws(seed, index, sub, stream, cls);
     return sample_guided<32>(ws, t, t.coarse, (int)m, out) ? GCR_OK
                                                             : set_err(GCR_EINTERNAL, "sample budget exhausted");
+}
+
+int gcr_host_guided_quanta(const double* probabilities, size_t n, uint32_t m, uint64_t* q_out, uint64_t* Q_out) {
+    if (!q_out || !Q_out) return set_err(GCR_EINVAL, "null argument");
+    return guard([&]() -> int {
+        std::vector<double> tab;
+        GuidedTable t{};
+        if (int e = build_guided(probabilities, n, m, tab, t)) return e;
+        *Q_out = build_quanta(probabilities, n, t.total, q_out);
+        return GCR_OK;
+    });
+}
+
+int gcr_host_guided_iterations(uint64_t mass, uint64_t Q, uint32_t m, double confidence, uint64_t* out) {
+    if (!out) return set_err(GCR_EINVAL, "null argument");
+    if (Q == 0 || Q >= (1ull << 52) || mass > Q)
+        return set_err(GCR_EINVAL, "guided stop: need 0 < Q < 2^52 and mass <= Q");
+    *out = iteration_number_guided(mass, Q, m, std::log(1.0 - confidence));
+    return GCR_OK;
 }
 
 int gcr_debug_math(gcr_ctx* ctx, int op, const double* a, const double* b, size_t n, double* out) {

@@ -312,6 +312,13 @@ hipError_t launch_mask_geo(const DevProblem& p, const GeoModel& model, int rule,
 hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc, uint32_t nh, uint64_t slot0,
                              uint32_t m, double Tm, BatchRecord* out, hipStream_t stream,
                              const uint32_t* hmap = nullptr, const uint32_t* hcount = nullptr);
+// The guided stop's measure of `nmodels` models (guided_stop.h): count[k] the
+// correspondences with r^2 <= T under models[k] (the scorers' residual: equal
+// to launch_score_geo's n0) and mass[k] the sum of their quanta (quanta: N
+// entries in device memory).  One workgroup per model, no atomics; the sums
+// are exact integers, the same for every reduction order.
+hipError_t launch_inlier_mass_geo(const DevProblem& p, double T, const GeoModel* models, uint32_t nmodels,
+                                  const uint64_t* quanta, uint32_t* count, uint64_t* mass, hipStream_t stream);
 // deferred selection of `count` consecutive batches in one launch (one
 // workgroup per batch): batch b's score arrays, inc, hmap at offset b * stride,
 // its hcount at hcount + b, its slots from slot0 + b * nh / per, its record out[b]

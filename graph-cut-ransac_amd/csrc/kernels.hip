@@ -5305,6 +5305,63 @@ hipError_t launch_sqres_geo(const DevProblem& p, const GeoModel& model, double* 
     return hipGetLastError();
 }
 
+// inlier count and inlier mass (guided_stop.h) of each model: one workgroup
+// per model, its threads stride over the correspondences with the scorers'
+// residual and threshold test, then the integer partials are reduced across
+// the wave (shuffles) and across the workgroup's waves (LDS).  Sums of
+// integers below 2^53: the result does not depend on the reduction tree.
+template <int KIND>
+__global__ __launch_bounds__(kScoreBlock) void k_inlier_mass(DevClass c, double T, const GeoModel* __restrict__ models,
+                                                             const uint64_t* __restrict__ quanta,
+                                                             uint32_t* __restrict__ count,
+                                                             uint64_t* __restrict__ mass) {
+    constexpr int kWaves = kScoreBlock / 64;
+    __shared__ uint32_t s_cnt[kWaves];
+    __shared__ uint64_t s_mass[kWaves];
+    const GeoModel m = models[blockIdx.x];
+    uint32_t cnt = 0;
+    uint64_t ms = 0;
+    for (uint64_t i = threadIdx.x; i < c.n; i += kScoreBlock) {
+        const double r2 = geo_sq_residual<KIND>(c.x[i], c.y[i], c.a[i], c.c0[i], m.h);
+        const bool inl = r2 <= T;
+        cnt += inl ? 1u : 0u;
+        ms += inl ? quanta[i] : 0ull;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        cnt += (uint32_t)__shfl_xor((int)cnt, d);
+        ms += (uint64_t)__shfl_xor((unsigned long long)ms, d);
+    }
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) {
+        s_cnt[wave] = cnt;
+        s_mass[wave] = ms;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        uint32_t ct = 0;
+        uint64_t mt = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; ++k) {
+            ct += s_cnt[k];
+            mt += s_mass[k];
+        }
+        count[blockIdx.x] = ct;
+        mass[blockIdx.x] = mt;
+    }
+}
+
+hipError_t launch_inlier_mass_geo(const DevProblem& p, double T, const GeoModel* models, uint32_t nmodels,
+                                  const uint64_t* quanta, uint32_t* count, uint64_t* mass, hipStream_t stream) {
+    if (nmodels == 0) return hipSuccess;
+    if (p.solver != 3 && p.solver != 4) return hipErrorInvalidValue;
+    if (models == nullptr || quanta == nullptr || count == nullptr || mass == nullptr) return hipErrorInvalidValue;
+    const dim3 grid(nmodels), block(kScoreBlock);
+    if (p.solver == 4) hipLaunchKernelGGL(k_inlier_mass<4>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
+    else hipLaunchKernelGGL(k_inlier_mass<3>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
+    return hipGetLastError();
+}
+
 hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc, uint32_t nh, uint64_t slot0,
                              uint32_t m, double Tm, BatchRecord* out, hipStream_t stream, const uint32_t* hmap,
                              const uint32_t* hcount) {

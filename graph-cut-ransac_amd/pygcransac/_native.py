@@ -22,6 +22,7 @@ GCR_EINVAL = -22
 GCR_ENODEV = -19
 SOLVER_SCALE3, SOLVER_SCALE3_ORIGINAL, SOLVER_SIFT22, SOLVER_HOMOGRAPHY4, SOLVER_FUNDAMENTAL7 = 0, 1, 2, 3, 4
 FLAG_NO_LO = 1
+FLAG_GUIDED_STOP = 2     # guided sampling only: the adaptive stop on the inlier mass (csrc/guided_stop.h)
 
 
 class Params(C.Structure):
@@ -205,6 +206,11 @@ def _load():
     L.gcr_debug_sample_h.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, u32p]
     L.gcr_measure_generate_h.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, dp]
     L.gcr_host_solve_minimal.argtypes = [C.c_int, dp, C.c_size_t, u32p, dp, u32p]
+    # the guided stop (GCR_FLAG_GUIDED_STOP): its host definition and its kernel alone
+    u64p = C.POINTER(C.c_uint64)
+    L.gcr_host_guided_quanta.argtypes = [vp, C.c_size_t, C.c_uint32, u64p, u64p]
+    L.gcr_host_guided_iterations.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, u64p]
+    L.gcr_debug_inlier_mass_h.argtypes = [vp, C.POINTER(Params), dp, C.c_uint32, u32p, u64p]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

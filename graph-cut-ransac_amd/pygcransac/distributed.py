@@ -246,7 +246,10 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     device); otherwise through `dist` in a Python callback (gloo or RCCL).
     `probabilities` (homography / fundamental matrix only; one weight per
     correspondence) switches the problem to guided sampling
-    (gcr_problem_set_probabilities), the same on every rank.
+    (gcr_problem_set_probabilities), the same on every rank; with them,
+    ``params={"flags": _native.FLAG_GUIDED_STOP, ...}`` stops the run on the
+    inlier mass (every rank computes the chain members' masses itself: the
+    exchanged records are the same).
     Returns (H (3, 3) or None, masks tuple, stats dict, rect model record)."""
     import ctypes as C
 

@@ -442,7 +442,7 @@ def _as_probabilities(probabilities, n, m):
 
 def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                          spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
-                         batch_slots, return_stats, min_rows, neighborhood_size):
+                         batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False):
     for name, v in (("h1", h1), ("w1", w1), ("h2", h2), ("w2", w2)):
         _as_double(v, name)
     sampler_id = _as_size_t(sampler, "sampler")
@@ -453,6 +453,9 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
         raise ValueError("The uniform sampler (0) takes no probabilities; they must be empty (sampler=3 uses them).")
     if sampler_id == 3 and probabilities is None:
         raise ValueError("sampler=3 (guided) needs probabilities, one per correspondence.")
+    if guided_stop and sampler_id != 3:
+        raise ValueError("guided_stop=True stops on the guided sampler's inlier mass: it needs sampler=3 "
+                         "with probabilities.")
     f = _as_features(correspondences)
     if f.ndim != 2:
         raise ValueError("Number of dimensions must be 2.")
@@ -463,6 +466,8 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     f = np.ascontiguousarray(f)
     p = _params(threshold, 2.0, spatial_coherence_weight, min_iters, max_iters, lo_number, seed, conf, batch_slots)
     _set_grid(p, f, h1, w1, h2, w2, neighborhood_size)
+    if guided_stop:
+        p.flags |= N.FLAG_GUIDED_STOP
     mask = np.zeros(n, dtype=np.uint8)
     M = np.zeros(9, dtype=np.float64)
     st = N.Stats()
@@ -483,7 +488,7 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
 
 def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                    spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
-                   neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False):
+                   neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False, guided_stop=False):
     """4-point homography with graph-cut LO -- an EXTENSION (SURVEY.md §8(f)
     row 3): this fork has no homography estimator (finding 0.1); the argument
     names and order follow upstream pygcransac's findHomography.
@@ -499,7 +504,14 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     holds one weight per correspondence (finite, >= 0, at least 4 of them > 0),
     and every minimal sample of the main loop draws correspondence i with
     probability w[i] / sum(w); a zero weight is never drawn, and local
-    optimisation's inner sampler stays uniform.  ``threshold`` is the inlier threshold in pixels
+    optimisation's inner sampler stays uniform.  The adaptive stop is the
+    reference's bound on the inlier share I / N, which describes uniform
+    sampling; ``guided_stop=True`` (``sampler=3`` only, else ValueError) takes
+    the same bound on the best model's inlier MASS, the inliers' share of the
+    weights (csrc/guided_stop.h), so a run with informative weights returns as
+    soon as its own sampler justifies it.  With all-equal weights both stops
+    are identical.  The bound is meaningful when no single weight dominates
+    the sum.  ``threshold`` is the inlier threshold in pixels
     of the second image (MSAC threshold 2.25 * threshold, as the rectification
     solvers).
 
@@ -508,17 +520,19 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     return _correspondence_call(N.lib.gcr_find_homography, N.lib.gcr_find_homography_guided, correspondences,
                                 h1, w1, h2, w2, probabilities, threshold, conf, spatial_coherence_weight, max_iters,
                                 min_iters, sampler, lo_number,
-                                seed, device, batch_slots, return_stats, 4, neighborhood_size)
+                                seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop)
 
 
 def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                           spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50,
-                          *, neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False):
+                          *, neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
+                          guided_stop=False):
     """7-point fundamental matrix with graph-cut LO -- an EXTENSION like
     findHomography (same arguments, the same neighbourhood grid; upstream
     pygcransac's findFundamentalMatrix order).  The residual is the Sampson distance in pixels; a sample yields up
     to three models, each scored.  ``sampler=3`` with ``probabilities`` (at least
-    7 of them > 0) guides the 7-point samples as it does findHomography's.
+    7 of them > 0) guides the 7-point samples as it does findHomography's, and
+    ``guided_stop=True`` stops such a run on the inlier mass, as there.
 
     Returns ``(F, inliers)`` with F (3, 3), unit Frobenius norm and
     x2^T F x1 = 0, or ``(None, inliers)``.
@@ -526,4 +540,4 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
     return _correspondence_call(N.lib.gcr_find_fundamental_matrix, N.lib.gcr_find_fundamental_matrix_guided,
                                 correspondences, h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
-                                seed, device, batch_slots, return_stats, 7, neighborhood_size)
+                                seed, device, batch_slots, return_stats, 7, neighborhood_size, guided_stop)

@@ -37,7 +37,10 @@ extern "C" {
 
 /* Guided sampling (gcr_problem_set_probabilities, the *_guided entries and
  * their debug hooks) was added without a version change: every addition is a
- * new function, no struct changed size or layout, so the version stays 5. */
+ * new function, no struct changed size or layout, so the version stays 5.
+ * The same holds for the guided stop: GCR_FLAG_GUIDED_STOP is a new bit of
+ * gcr_params.flags (a call that leaves it clear runs as before), its host
+ * and debug entries are new functions. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -70,7 +73,7 @@ typedef struct gcr_params {
     double confidence;                   /* settings.h:60 default 0.95 (not set by Python) */
     uint64_t seed;                       /* extension: Philox key (reference is unseeded) */
     uint32_t batch_slots;                /* extension: outer-iteration slots per launch, 0 = auto */
-    uint32_t flags;                      /* bit 0: disable local optimisation (bench only) */
+    uint32_t flags;                      /* GCR_FLAG_*: bit 0 disables local optimisation (bench only), bit 1 the guided stop */
     /* extension (homography / fundamental matrix only): the neighbourhood grid
      * over (x1, y1, x2, y2) whose cells give labeling()'s pairwise terms
      * (GridNeighborhoodGraph<4>, grid_neighborhood_graph.h:229-301); cell
@@ -85,6 +88,13 @@ typedef struct gcr_params {
 } gcr_params;
 
 #define GCR_FLAG_NO_LO 1u
+/* Guided sampling only (a homography / fundamental-matrix problem with
+ * probabilities set; anything else, gcr_solve_batch's items included, is
+ * GCR_EINVAL): the adaptive stop uses the best model's inlier MASS, the
+ * inliers' share of the sampling weight, in place of its inlier share I / N
+ * (csrc/guided_stop.h is the definition).  With all-equal weights the two are
+ * the same bits.  Clear (the default): the reference's uniform bound. */
+#define GCR_FLAG_GUIDED_STOP 2u
 
 /* model.h: NormalizingTransform{x0,y0,s}, RectifyingHomography{h7,h8},
  * ScaleBased{alpha}, OrientationBased{phi}. */
@@ -176,9 +186,12 @@ int gcr_find_fundamental_matrix(gcr_ctx* ctx, const double* correspondences, siz
  * anything else is GCR_EINVAL).  Every minimal sample of the main loop draws
  * correspondence i with probability w[i] / sum(w) (csrc/guided.h is the
  * definition); a zero weight is never drawn.  Validity checks, solvers,
- * scoring, the adaptive stop and local optimisation (whose inner sampler
- * stays uniform) are unchanged.  probabilities == NULL: exactly the plain
- * entry. */
+ * scoring and local optimisation (whose inner sampler stays uniform) are
+ * unchanged.  The adaptive stop is the reference's uniform bound on I / N
+ * unless params->flags has GCR_FLAG_GUIDED_STOP: then it is the same formula
+ * on the best model's inlier mass W_I / W (csrc/guided_stop.h), which ends a
+ * run with informative weights as soon as its own sampler justifies it.
+ * probabilities == NULL: exactly the plain entry (the flag is then GCR_EINVAL). */
 int gcr_find_homography_guided(gcr_ctx* ctx, const double* correspondences, size_t n, const double* probabilities,
                                const gcr_params* params, uint8_t* mask_out, double* H_out, gcr_stats* stats_out);
 int gcr_find_fundamental_matrix_guided(gcr_ctx* ctx, const double* correspondences, size_t n,
@@ -351,6 +364,12 @@ int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, 
 int gcr_debug_score_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels, uint32_t* n0,
                       double* v0, double* tot);
 int gcr_debug_mask_h(gcr_problem* prob, const gcr_params* params, const double* H, int rule, uint8_t* mask_out);
+/* the guided stop's kernel alone (csrc/guided_stop.h) on a problem with
+ * probabilities set: per model of H (9 doubles each) the number of
+ * correspondences within the MSAC threshold 2.25 thr^2 (equal to
+ * gcr_debug_score_h's n0) and the sum of their quanta */
+int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels,
+                            uint32_t* count_out, uint64_t* mass_out);
 /* host-only: normalised least-squares homography of the listed
  * correspondences (the LO / final-refit fit); 1 = fitted, 0 = rejected */
 int gcr_host_fit_h(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* H_out);
@@ -401,6 +420,16 @@ int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t
  * gcr_problem_set_probabilities checks them, with m as the minimal size */
 int gcr_host_sample_guided(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls,
                            const double* probabilities, size_t n, uint32_t m, uint32_t* out);
+/* host-only: the guided stop's quanta (csrc/guided_stop.h) of raw weights,
+ * checked as gcr_problem_set_probabilities checks them with m as the minimal
+ * size: q_out[i] = (uint64_t)(w[i] / total * 2^(52 - bit_length(n))), *Q_out
+ * their sum (< 2^52; 0 is possible for n >= 2^26 only) */
+int gcr_host_guided_quanta(const double* probabilities, size_t n, uint32_t m, uint64_t* q_out, uint64_t* Q_out);
+/* host-only: the guided stop itself, the function the engine calls: the
+ * reference's iteration bound with ratio mass / Q for a minimal sample of m
+ * at `confidence` (UINT64_MAX where the reference's guard returns it).
+ * Q == 0, mass > Q or Q >= 2^52: GCR_EINVAL */
+int gcr_host_guided_iterations(uint64_t mass, uint64_t Q, uint32_t m, double confidence, uint64_t* out);
 /* device evaluation of the same primitives over arrays (GPU parity tests):
  * op 0 log(a), 1 pow_m3(a), 2 atan2(a, b), 3 a / b, 4 sqrt(a),
  * 5 clip_angle_small(a), 6 clip_angle(a), 8 round 3's log (dm_log_fd),

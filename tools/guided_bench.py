@@ -9,12 +9,17 @@
      and the generator's own time per launch (HIP events, gcr_measure_generate_h)
   3  wall time to 0.99 confidence through findFundamentalMatrix, the median of
      --calls calls: uniform against weights 1 / 0.05 on truth inliers / outliers
-     (the adaptive stop is the uniform sampler's in both), and the same calls
-     on a fixed budget of --budget iterations: time and truth inliers found
+     with the adaptive stop of the uniform sampler, and those weights with the
+     stop on the inlier mass (guided_stop=True); the same three lines at the H
+     shape (problem_h, N = 10 000, 80 % outliers); the cost of the stop's mass
+     launches (all-ones weights, flag set against clear: the same iterations);
+     and the F calls on a fixed budget of --budget iterations: time and truth
+     inliers found
 
 The legs of 1 and 2 alternate run by run inside one process.  --pkg points at
 another tree's graph-cut-ransac_amd (e.g. the parent commit's, with its own
-libgcr.so): a library without the guided entry points runs leg 1 only.
+libgcr.so): a library without the guided entry points runs leg 1 only, a tree
+without the guided stop leaves its lines out.
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -112,24 +117,73 @@ if guided_lib:
     out["ratio_guided_ones_flat_to_uniform"] = round(statistics.median(rates["guided_ones_flat"]) / u, 4)
 N.lib.gcr_problem_destroy(h)
 
+stop_lib = hasattr(N, "FLAG_GUIDED_STOP")        # the guided stop (GCR_FLAG_GUIDED_STOP) exists in this tree
+
+
+def latency_leg(fn, c, tr, t, lines, lo, hi):
+    """--calls timed calls of every line, the lines alternating call by call
+    (call -1 warms up); per line the median, the quartiles and what was found"""
+    acc = {name: ([], [], [], []) for name, _ in lines}
+    for r in range(-1, args.calls):
+        for name, kw in lines:
+            t0 = time.perf_counter()
+            M, mask, st = fn(c, 960, 1280, 960, 1280, threshold=t, conf=0.99, min_iters=lo, max_iters=hi,
+                             seed=100 + r, return_stats=True, **kw)
+            dt = (time.perf_counter() - t0) * 1e3
+            if r >= 0:
+                ms, its, inl, launches = acc[name]
+                ms.append(dt)
+                its.append(st["iteration_number"])
+                inl.append(int(mask[tr].sum()))
+                launches.append(st["launches"])
+    lat = {}
+    for name, (ms, its, inl, launches) in acc.items():
+        qs = statistics.quantiles(ms, n=4) if len(ms) > 1 else [ms[0]] * 3
+        lat[name] = {"median_ms": round(statistics.median(ms), 4), "q1_ms": round(qs[0], 4), "q3_ms": round(qs[2], 4),
+                     "ms": [round(v, 4) for v in ms], "median_iterations": statistics.median(its),
+                     "iterations": its, "launches": launches, "truth_inliers_found": inl,
+                     "truth_inliers": int(tr.sum())}
+    return lat
+
+
+def replayed_chunks(fn, c, t, kw, lo, hi):
+    """chunks one call replays (the exchange log's `collected` events)"""
+    os.environ["GCR_EXCHANGE_LOG"] = "1"
+    try:
+        fn(c, 960, 1280, 960, 1280, threshold=t, conf=0.99, min_iters=lo, max_iters=hi, seed=100, **kw)
+        return sum(1 for e in N.exchange_log() if e[0] == 3)
+    finally:
+        del os.environ["GCR_EXCHANGE_LOG"]
+
+
 if guided_lib and not args.no_latency:
-    w = np.where(truth, 1.0, 0.05)
-    for key, lo, hi in (("latency_to_0.99", 0, 10**7), (f"budget_{args.budget}", args.budget, args.budget)):
-        lat = {}
-        for name, kw in (("uniform", {}), ("guided", dict(probabilities=w, sampler=3))):
-            ms, its, inl = [], [], []
-            for r in range(-1, args.calls):       # call -1 warms up
-                t0 = time.perf_counter()
-                F, mask, st = pygcransac.findFundamentalMatrix(corr, 960, 1280, 960, 1280, threshold=thr, conf=0.99,
-                                                               min_iters=lo, max_iters=hi, seed=100 + r,
-                                                               return_stats=True, **kw)
-                dt = (time.perf_counter() - t0) * 1e3
-                if r >= 0:
-                    ms.append(dt)
-                    its.append(st["iteration_number"])
-                    inl.append(int(mask[truth].sum()))
-            lat[name] = {"median_ms": round(statistics.median(ms), 4), "ms": [round(v, 4) for v in ms],
-                         "median_iterations": statistics.median(its), "truth_inliers_found": inl,
-                         "truth_inliers": int(truth.sum())}
-        out[key] = lat
+    # leg 3 at the F shape (above) and the H shape: problem_h, N = 10 000, 80 % outliers
+    corr_h, truth_h, _, thr_h = S.problem_h(10_000, 0.8, seed=SEED)
+    corr_h = np.ascontiguousarray(corr_h)
+    shapes = (("", pygcransac.findFundamentalMatrix, corr, truth, thr),
+              ("h_", pygcransac.findHomography, corr_h, truth_h, thr_h))
+    for tag, fn, c, tr, t in shapes:
+        w = np.where(tr, 1.0, 0.05)
+        lines = [("uniform", {}), ("guided", dict(probabilities=w, sampler=3))]
+        if stop_lib:
+            lines.append(("guided_stop", dict(probabilities=w, sampler=3, guided_stop=True)))
+        out[tag + "latency_to_0.99"] = latency_leg(fn, c, tr, t, lines, 0, 10**7)
+        if tag == "":
+            out[f"budget_{args.budget}"] = latency_leg(fn, c, tr, t, lines[:2], args.budget, args.budget)
+        if stop_lib:
+            # the mass launches' cost: all-ones weights stop where the uniform
+            # bound stops them with the flag set or clear (the same iterations),
+            # so the difference is the launches
+            w1 = np.ones(len(c))
+            cost = latency_leg(fn, c, tr, t, [("ones_clear", dict(probabilities=w1, sampler=3)),
+                                              ("ones_stop", dict(probabilities=w1, sampler=3, guided_stop=True))],
+                               0, 10**7)
+            a, b = cost["ones_clear"], cost["ones_stop"]
+            chunks = replayed_chunks(fn, c, t, dict(probabilities=w1, sampler=3, guided_stop=True), 0, 10**7)
+            cost["same_iterations"] = a["iterations"] == b["iterations"]
+            cost["mass_launches_per_run"] = statistics.median(y - x for x, y in zip(a["launches"], b["launches"]))
+            cost["replayed_chunks_seed_100"] = chunks
+            cost["ms_per_run"] = round(b["median_ms"] - a["median_ms"], 4)
+            cost["ms_per_replayed_chunk"] = round((b["median_ms"] - a["median_ms"]) / max(chunks, 1), 4)
+            out[tag + "mass_launch_cost"] = cost
 print(json.dumps(out))
