@@ -592,7 +592,30 @@ struct gcr_problem {
         const char* e = getenv("GCR_GUIDED_FLAT");
         return (e && e[0] == '1') ? &gt_flat : &gt;
     }
+    // Essential matrix (solver 5): hc[0] and the device SoA hold the
+    // K-normalised correspondences, and dp.solver is 4, so scoring, masks,
+    // residuals and the inlier mass are the fundamental matrix's (squared
+    // Sampson distance).  Host only: the pixel columns (the neighbourhood
+    // grid is built over them) and the divisor that takes a pixel threshold
+    // to normalised coordinates.
+    std::vector<double> pix[4];
+    double thr_div = 1.0;
+    // what the generator launches get: the problem's own solver kind
+    DevProblem gen_dp() const {
+        DevProblem d = dp;
+        d.solver = solver;
+        return d;
+    }
+    // the residual threshold of params in the units of hc[0]
+    double thr0(const gcr_params& prm) const {
+        return solver == GCR_SOLVER_ESSENTIAL5 ? prm.scale_residual_thresh / thr_div : prm.scale_residual_thresh;
+    }
 };
+
+// the correspondence estimators (GeoModel, N x 4 rows)
+static inline bool is_corr(int solver) {
+    return solver == GCR_SOLVER_HOMOGRAPHY4 || solver == GCR_SOLVER_FUNDAMENTAL7 || solver == GCR_SOLVER_ESSENTIAL5;
+}
 
 namespace {
 
@@ -1233,13 +1256,48 @@ hipStream_t aux_stream(gcr_ctx* ctx) {
     return ctx->aux;
 }
 
+// A calibration matrix the essential-matrix entries accept: row-major 3 x 3,
+// finite, third row exactly (0, 0, 1), K[1][0] == 0, both focal lengths > 0
+// (skew allowed).
+int check_calibration(const double* K, const char* name) {
+    if (!K) return set_err(GCR_EINVAL, "%s: null calibration matrix", name);
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(K[k])) return set_err(GCR_EINVAL, "%s: entry %d is not finite", name, k);
+    if (K[6] != 0.0 || K[7] != 0.0 || K[8] != 1.0)
+        return set_err(GCR_EINVAL, "%s: the third row must be exactly (0, 0, 1)", name);
+    if (K[3] != 0.0) return set_err(GCR_EINVAL, "%s: K[1][0] must be 0", name);
+    if (!(K[0] > 0.0) || !(K[4] > 0.0)) return set_err(GCR_EINVAL, "%s: the focal lengths K[0][0], K[1][1] must be > 0", name);
+    return GCR_OK;
+}
+
+// x^ = K^-1 x in closed form: y^ = (y - cy) / fy, x^ = ((x - cx) - s y^) / fx
+inline void normalise_point(const double* K, double x, double y, double& xh, double& yh) {
+    yh = (y - K[5]) / K[4];
+    xh = ((x - K[2]) - K[1] * yh) / K[0];
+}
+
+// upstream's rule: a pixel threshold over the mean of the four focal lengths
+inline double essential_thr_div(const double* K1, const double* K2) { return (((K1[0] + K1[4]) + K2[0]) + K2[4]) / 4.0; }
+
+// K1 / K2 (both or neither): an essential-matrix problem (solver 5) from N x 4
+// pixel rows
 int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
-                 gcr_problem** out, bool shared_workspace = false) {
+                 gcr_problem** out, bool shared_workspace = false, const double* K1 = nullptr,
+                 const double* K2 = nullptr) {
+    const bool ess = solver == GCR_SOLVER_ESSENTIAL5;
+    if (ess && (K1 == nullptr || K2 == nullptr))
+        return set_err(GCR_EINVAL, "solver 5 (essential matrix) needs the calibration matrices: use "
+                                   "gcr_problem_create_essential or gcr_find_essential_matrix");
     if (!ctx || !out) return set_err(GCR_EINVAL, "null context or output pointer");
-    if (solver < 0 || solver > 4) return set_err(GCR_EINVAL, "unknown solver %d", solver);
+    if (solver < 0 || solver > 5) return set_err(GCR_EINVAL, "unknown solver %d", solver);
     const int K = solver == 2 ? 2 : 1;
-    const size_t m0 = solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : 3;
+    const size_t m0 = solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3;
     if (!f0 || (K == 2 && !f1)) return set_err(GCR_EINVAL, "null feature pointer");
+    if (ess) {
+        if (n0 < m0) return set_err(GCR_EINVAL, "an essential matrix needs at least 5 correspondences, got %zu", n0);
+        if (int e = check_calibration(K1, "K1")) return e;
+        if (int e = check_calibration(K2, "K2")) return e;
+    }
     if (n0 < m0 || (K == 2 && n1 < 2))
         return set_err(GCR_EINTERNAL, "Data set smaller than minimal sample size for corresponding data type");
     if (n0 > 0xffffffffull || n1 > 0xffffffffull) return set_err(GCR_EINVAL, "too many features");
@@ -1248,6 +1306,21 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
     P->ctx = ctx;
     P->solver = solver;
     P->K = K;
+    // essential matrix: normalised rows from here on, the pixels kept as columns
+    std::vector<double> nrm;
+    if (ess) {
+        nrm.resize(4 * n0);
+        for (int q = 0; q < 4; ++q) P->pix[q].resize(n0);
+        for (size_t i = 0; i < n0; ++i) {
+            for (int q = 0; q < 4; ++q) P->pix[q][i] = f0[4 * i + q];
+            normalise_point(K1, f0[4 * i], f0[4 * i + 1], nrm[4 * i], nrm[4 * i + 1]);
+            normalise_point(K2, f0[4 * i + 2], f0[4 * i + 3], nrm[4 * i + 2], nrm[4 * i + 3]);
+        }
+        f0 = nrm.data();
+        P->thr_div = essential_thr_div(K1, K2);
+    }
+    // the host / device classes and the kernels' KIND: the fundamental matrix's
+    const int dsolver = ess ? GCR_SOLVER_FUNDAMENTAL7 : solver;
     const size_t ns[2] = {n0, K == 2 ? n1 : 0};
     std::vector<std::pair<const char*, Clock::time_point>> st;      // GCR_LO_TRACE: "gcr SETUP:"
     if (g_lo_trace) st.emplace_back("start", Clock::now());
@@ -1285,10 +1358,10 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
     if (g_lo_trace) st.emplace_back("ws", Clock::now());
     double* hst = P->w->feat_stage.p;
     const size_t off[2] = {0, 5 * np[0]};
-    const FillOut fo = fill_host_classes(solver, f0, n0, f1, n1, P->hc, hst, np, off);
+    const FillOut fo = fill_host_classes(dsolver, f0, n0, f1, n1, P->hc, hst, np, off);
     if (solver <= 2) P->scales_ok = fo.scales_ok;
     if (g_lo_trace) st.emplace_back("fill", Clock::now());
-    P->dp.solver = solver;
+    P->dp.solver = dsolver;
     for (int c = 0; c < 2; ++c) {
         DevClass& d = P->dp.cls[c];
         d.n = (uint32_t)ns[c];
@@ -1593,7 +1666,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static bool valid(int, const Model&) { return true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
-        return launch_generate_geo(P->dp, seed, s0, n, inc, m, s, P->guided());
+        return launch_generate_geo(P->gen_dp(), seed, s0, n, inc, m, s, P->guided());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1652,7 +1725,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     }
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
-        hipError_t e = launch_generate_geo(P->dp, seed, s0, n, b.inc, b.models, s, P->guided());
+        hipError_t e = launch_generate_geo(P->gen_dp(), seed, s0, n, b.inc, b.models, s, P->guided());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -1732,8 +1805,9 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
         return launch_score_geo(P->dp, T[0], m, inc, std::max<uint32_t>(live, 1u), out, s, P->w->hmap.p,
                                 P->w->hcount.p);
     }
-    static size_t per(gcr_problem* P) { return P->solver == 4 ? kFModels : 1; }
+    static size_t per(gcr_problem* P) { return P->solver == 4 ? kFModels : P->solver == 5 ? kEModels : 1; }
     static bool fit(gcr_problem* P, const std::vector<uint32_t>* lists, Model& out, bool) {
+        if (P->solver == 5) return fit_e5_nonminimal(P->hc[0], lists[0], out);
         if (P->solver == 4) return fit_f8_nonminimal(P->hc[0], lists[0], out);
         return fit_h4_nonminimal(P->hc[0], lists[0], out);
     }
@@ -1752,6 +1826,10 @@ struct FundTraits : GeoTraits {     // up to kFModels models per sample
     }
 };
 
+struct EssTraits : FundTraits {      // up to kEModels models per sample (ess.h)
+    static constexpr size_t kPer = kEModels;
+};
+
 constexpr int kMaxLOSample = 64;     // largest LO sample: 7 x the largest minimal sample (7)
 
 template <class Tr>
@@ -1765,9 +1843,9 @@ public:
     }
     RunnerT(gcr_problem* P, const gcr_params& prm) : P_(P), prm_(prm), s_(P->ctx->stream) {
         K_ = P->K;
-        m_[0] = P->solver == 2 ? 2 : P->solver == 3 ? 4 : P->solver == 4 ? 7 : 3;
+        m_[0] = P->solver == 2 ? 2 : P->solver == 3 ? 4 : P->solver == 4 ? 7 : P->solver == 5 ? 5 : 3;
         m_[1] = 2;
-        thr_[0] = prm.scale_residual_thresh;
+        thr_[0] = P->thr0(prm);
         thr_[1] = prm.orientation_residual_thresh;
         for (int c = 0; c < 2; ++c) {
             Tm_[c] = (2.25 * thr_[c]) * thr_[c];            // MSAC_scoring_function.hpp:64
@@ -3001,7 +3079,10 @@ private:
             graph_state_ = 0;
             if (P_->solver >= 3 && prm_.cell_number > 0 && prm_.spatial_coherence_weight > 0) {
                 const HostClass& c = P_->hc[0];
-                const double* cols[4] = {c.x.data(), c.y.data(), c.a.data(), c.c0.data()};
+                // essential matrix: the grid lies over the pixels
+                const bool px = P_->solver == GCR_SOLVER_ESSENTIAL5;
+                const double* cols[4] = {px ? P_->pix[0].data() : c.x.data(), px ? P_->pix[1].data() : c.y.data(),
+                                         px ? P_->pix[2].data() : c.a.data(), px ? P_->pix[3].data() : c.c0.data()};
                 // a cell size of 0 (image size unknown to the caller): the
                 // column's extent (largest finite coordinate + 1, at least 1)
                 // over the cells, as pygcransac.grid_cell_sizes computes it
@@ -4151,6 +4232,7 @@ private:
 using Runner = RunnerT<RectTraits>;
 using GeoRunner = RunnerT<GeoTraits>;
 using FundRunner = RunnerT<FundTraits>;
+using EssRunner = RunnerT<EssTraits>;
 
 }  // namespace
 
@@ -4233,14 +4315,14 @@ uint64_t build_quanta(const double* w, size_t n, double total, uint64_t* q) {
     return Q;
 }
 
-size_t minimal_size(int solver) { return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : 3; }
+size_t minimal_size(int solver) { return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3; }
 
 // GCR_FLAG_GUIDED_STOP is valid only on a problem that samples guided
 int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
     if ((params->flags & GCR_FLAG_GUIDED_STOP) == 0) return GCR_OK;
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling exists for homography and "
-                                   "fundamental-matrix problems only");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling exists for homography, "
+                                   "fundamental- and essential-matrix problems only");
     if (prob->gt.cdf == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
                                    "(gcr_problem_set_probabilities)");
@@ -4255,7 +4337,7 @@ int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
 // awaited first (no run ever consumes a chunk of an earlier run, so waiting
 // for it discards it), then the table is replaced.
 int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
+    if (!is_corr(prob->solver))
         return set_err(GCR_EINVAL, "guided sampling: homography and fundamental-matrix problems only");
     std::vector<double> tab;
     GuidedTable t{};
@@ -4430,6 +4512,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
             fill_stats(stats_out, r.stats());
             return total;
         };
+        if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
         return prob->solver == GCR_SOLVER_HOMOGRAPHY4 ? go(GeoRunner(prob, *params)) : go(Runner(prob, *params));
     });
@@ -4452,6 +4535,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
             fill_stats(stats_out, r.stats());
             return total;
         };
+        if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
         return go(Runner(prob, *params));
@@ -4530,6 +4614,7 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
             return total;
         };
         try {
+            if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
             return go(Runner(prob, *params));
@@ -4562,6 +4647,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
             fill_stats(stats_out, r.stats());
             return GCR_OK;
         };
+        if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
         return prob->solver == GCR_SOLVER_HOMOGRAPHY4 ? go(GeoRunner(prob, *params)) : go(Runner(prob, *params));
     });
@@ -4575,7 +4661,8 @@ int gcr_problem_verify_batch(gcr_problem* prob, const gcr_params* params, uint64
 
 static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                        const gcr_params* params, uint8_t* m0, uint8_t* m1, double* H, gcr_rect_model* model,
-                       gcr_stats* stats, const double* probabilities = nullptr) {
+                       gcr_stats* stats, const double* probabilities = nullptr, const double* K1 = nullptr,
+                       const double* K2 = nullptr) {
     if (!ctx) return set_err(GCR_EINVAL, "null context");
     if (int e = check_params(params, solver)) return e;
     if ((params->flags & GCR_FLAG_GUIDED_STOP) != 0 && probabilities == nullptr)
@@ -4583,7 +4670,7 @@ static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, co
                                    "gcr_solve_batch's items carry no probabilities");
     const auto t0 = Clock::now();
     gcr_problem* prob = nullptr;
-    int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true); });
+    int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true, K1, K2); });
     if (rc != GCR_OK) return rc;
     if (probabilities != nullptr) rc = set_probabilities(prob, probabilities, n0);
     const double setup = ms_since(t0);
@@ -4719,6 +4806,93 @@ int gcr_find_fundamental_matrix_guided(gcr_ctx* ctx, const double* correspondenc
                        nullptr, stats_out, probabilities);
 }
 
+int gcr_find_essential_matrix(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                              const double* K2, const double* probabilities, const gcr_params* params,
+                              uint8_t* mask_out, double* E_out, gcr_stats* stats_out) {
+    if (!K1 || !K2) return set_err(GCR_EINVAL, "null calibration matrix");
+    return run_oneshot(ctx, GCR_SOLVER_ESSENTIAL5, correspondences, n, nullptr, 0, params, mask_out, nullptr, E_out,
+                       nullptr, stats_out, probabilities, K1, K2);
+}
+
+int gcr_problem_create_essential(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                                 const double* K2, gcr_problem** out) {
+    if (!K1 || !K2) return set_err(GCR_EINVAL, "null calibration matrix");
+    return guard([&]() {
+        return make_problem(ctx, GCR_SOLVER_ESSENTIAL5, correspondences, n, nullptr, 0, out, false, K1, K2);
+    });
+}
+
+int gcr_host_essential_normalise(const double* correspondences, size_t n, const double* K1, const double* K2,
+                                 double threshold, double* normalised_out, double* threshold_out) {
+    if (int e = check_calibration(K1, "K1")) return e;
+    if (int e = check_calibration(K2, "K2")) return e;
+    if (n > 0 && (!correspondences || !normalised_out)) return set_err(GCR_EINVAL, "null argument");
+    for (size_t i = 0; i < n; ++i) {
+        const double* r = correspondences + 4 * i;
+        double* o = normalised_out + 4 * i;
+        normalise_point(K1, r[0], r[1], o[0], o[1]);
+        normalise_point(K2, r[2], r[3], o[2], o[3]);
+    }
+    if (threshold_out) *threshold_out = threshold / essential_thr_div(K1, K2);
+    return GCR_OK;
+}
+
+int gcr_host_generate_e(const double* correspondences, size_t n, uint64_t seed, uint64_t slot0, uint32_t nslots,
+                        int threads, uint8_t* inc_out, double* models_out) {
+    if (!correspondences || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
+    if (n < 5 || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    return guard([&]() -> int {
+        // k_generate_e's rule, slot by slot: attempts 0..100, the first success wins
+        auto work = [&](uint32_t lo, uint32_t hi) {
+            for (uint32_t s = lo; s < hi; ++s) {
+                uint8_t* oi = inc_out + (size_t)kEModels * s;
+                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)kEModels * s;
+                int cnt = 0;
+                uint32_t a = 0;
+                GeoModel ms[kEModels];
+                for (; a < 101 && cnt == 0; ++a) {
+                    uint32_t idx[5];
+                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
+                    if (!sample_distinct<5>(ws, n, 5, idx)) continue;
+                    double x1[5], y1[5], x2[5], y2[5];
+                    for (int j = 0; j < 5; ++j) {
+                        const double* r = correspondences + 4 * (size_t)idx[j];
+                        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
+                    }
+                    cnt = solve_e5(x1, y1, x2, y2, ms);
+                }
+                for (int q = 0; q < kEModels; ++q) {
+                    out[q] = q < cnt ? ms[q] : default_geo();
+                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
+        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
+        work(0, std::min(nslots, step));
+        for (auto& t : pool) t.join();
+        return GCR_OK;
+    });
+}
+
+int gcr_host_fit_e(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* E_out) {
+    if (!correspondences || !idx || !E_out) return set_err(GCR_EINVAL, "bad arguments");
+    return guard([&]() -> int {
+        HostClass hc[2];
+        fill_host_classes(GCR_SOLVER_FUNDAMENTAL7, correspondences, n, nullptr, 0, hc);
+        std::vector<uint32_t> list(idx, idx + k);
+        for (uint32_t i : list)
+            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
+        GeoModel m;
+        if (!fit_e5_nonminimal(hc[0], list, m)) return 0;
+        for (int q = 0; q < 9; ++q) E_out[q] = m.h[q];
+        return 1;
+    });
+}
+
 int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* F_out) {
     if (!correspondences || !idx || !F_out) return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
@@ -4738,8 +4912,8 @@ int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx,
 int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc_out,
                          double* H_out) {
     if (!prob || !inc_out || !H_out) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
@@ -4747,7 +4921,7 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->inc.ensure(nh);
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_generate_geo(prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
+        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -4758,8 +4932,8 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
 int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
                        uint32_t* idx_out) {
     if (!prob || !idx_out) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
@@ -4767,7 +4941,7 @@ int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_
         DevBuf<uint32_t> out;
         out.ensure(std::max<size_t>(cnt, 1));
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_debug_sample(prob->dp, seed, slot0, nslots, attempt, out.p, s, prob->guided()));
+        HIPC(launch_debug_sample(prob->gen_dp(), seed, slot0, nslots, attempt, out.p, s, prob->guided()));
         HIPC(hipMemcpyAsync(idx_out, out.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
         return GCR_OK;
@@ -4777,8 +4951,8 @@ int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_
 int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, int reps,
                            double* ms_out) {
     if (!prob || !ms_out || reps < 1 || nslots == 0) return set_err(GCR_EINVAL, "invalid argument");
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
@@ -4787,10 +4961,10 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
         // one untimed launch first (code object load, caches)
-        HIPC(launch_generate_geo(prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
+        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
         HIPC(hipEventRecord(prob->ctx->ev0, s));
         for (int r = 0; r < reps; ++r)
-            HIPC(launch_generate_geo(prob->dp, seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
+            HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
                                      prob->w->gmodels.p, s, prob->guided()));
         HIPC(hipEventRecord(prob->ctx->ev1, s));
         HIPC(hipEventSynchronize(prob->ctx->ev1));
@@ -4804,8 +4978,8 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
 int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, const uint32_t* idx,
                            double* models_out, uint32_t* count_out) {
     if (!correspondences || !idx || !models_out || !count_out) return set_err(GCR_EINVAL, "null argument");
-    if (solver != GCR_SOLVER_HOMOGRAPHY4 && solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "gcr_host_solve_minimal: homography or fundamental matrix");
+    if (!is_corr(solver))
+        return set_err(GCR_EINVAL, "gcr_host_solve_minimal: homography, fundamental or essential matrix");
     const int m = (int)minimal_size(solver);
     double x1[7], y1[7], x2[7], y2[7];
     for (int j = 0; j < m; ++j) {
@@ -4825,6 +4999,15 @@ int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, 
         *count_out = 1;
         return GCR_OK;
     }
+    if (solver == GCR_SOLVER_ESSENTIAL5) {
+        // kernels.hip attempt_e: normalised rows, up to kEModels models
+        GeoModel ms[kEModels];
+        const int cnt = solve_e5(x1, y1, x2, y2, ms);
+        for (int k = 0; k < cnt; ++k)
+            for (int q = 0; q < 9; ++q) models_out[9 * k + q] = ms[k].h[q];
+        *count_out = (uint32_t)cnt;
+        return GCR_OK;
+    }
     // kernels.hip attempt_f and the winning lane's models
     F7Basis b;
     if (solve_f7_basis(x1, y1, x2, y2, b) == 0) return GCR_OK;
@@ -4841,13 +5024,13 @@ int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, 
 int gcr_debug_score_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels, uint32_t* n0,
                       double* v0, double* tot) {
     if (!prob || !params || !H || !n0 || !v0 || !tot) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
         hipStream_t s = prob->ctx->stream;
-        const double thr = params->scale_residual_thresh;
+        const double thr = prob->thr0(*params);
         const double T = (2.25 * thr) * thr;
         prob->w->lo_gmodels.ensure(nmodels);
         prob->w->lo_sb.ensure(nmodels);
@@ -4869,13 +5052,13 @@ int gcr_debug_score_h(gcr_problem* prob, const gcr_params* params, const double*
 
 int gcr_debug_mask_h(gcr_problem* prob, const gcr_params* params, const double* H, int rule, uint8_t* mask_out) {
     if (!prob || !params || !H || !mask_out) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
         hipStream_t s = prob->ctx->stream;
-        const double thr = params->scale_residual_thresh;
+        const double thr = prob->thr0(*params);
         double T;
         if (rule == 0) T = (2.25 * thr) * thr;
         else { const double t = 1.5 * thr; T = t * t; }
@@ -4894,8 +5077,8 @@ int gcr_debug_mask_h(gcr_problem* prob, const gcr_params* params, const double* 
 int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels,
                             uint32_t* count_out, uint64_t* mass_out) {
     if (!prob || !params || !H || !count_out || !mass_out) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver != GCR_SOLVER_HOMOGRAPHY4 && prob->solver != GCR_SOLVER_FUNDAMENTAL7)
-        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental) problem");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
     if (prob->gq == nullptr)
         return set_err(GCR_EINVAL, "the inlier mass needs guided sampling: the problem has no probabilities");
     if (nmodels == 0) return GCR_OK;
@@ -4903,7 +5086,7 @@ int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const d
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
         hipStream_t s = prob->ctx->stream;
-        const double thr = params->scale_residual_thresh;
+        const double thr = prob->thr0(*params);
         const double T = (2.25 * thr) * thr;
         Workspace* w = prob->w;
         w->gm_models.ensure(nmodels);

@@ -637,4 +637,54 @@ bool fit_f8_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, Geo
     return denormalize_f(f2, s1, mx1, my1, s2, mx2, my2, out.h);
 }
 
+bool fit_e5_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, GeoModel& out) {
+    const size_t n = idx.size();
+    if (n < 5) return false;
+    if (n == 5) {
+        double x1[5], y1[5], x2[5], y2[5];
+        for (int i = 0; i < 5; ++i) {
+            x1[i] = c.x[idx[i]]; y1[i] = c.y[idx[i]]; x2[i] = c.a[idx[i]]; y2[i] = c.c0[idx[i]];
+        }
+        GeoModel ms[kEModels];
+        if (solve_e5(x1, y1, x2, y2, ms) == 0) return false;
+        out = ms[0];
+        return true;
+    }
+    double ata[9][9] = {};
+    for (size_t i = 0; i < n; ++i) {
+        const double u1 = c.x[idx[i]], v1 = c.y[idx[i]], u2 = c.a[idx[i]], v2 = c.c0[idx[i]];
+        const double r[9] = {u2 * u1, u2 * v1, u2, v2 * u1, v2 * v1, v2, u1, v1, 1.0};
+        for (int p = 0; p < 9; ++p)
+            for (int q = p; q < 9; ++q) ata[p][q] += r[p] * r[q];
+    }
+    for (int p = 0; p < 9; ++p)
+        for (int q = 0; q < p; ++q) ata[p][q] = ata[q][p];
+    double V[9][9], D[9];
+    jacobi_eigen<9>(ata, V, D);
+    // the four smallest eigenvalues, ascending, the lower index first on ties
+    bool used[9] = {};
+    double bs[4][9];
+    for (int t = 0; t < 4; ++t) {
+        int k = -1;
+        for (int i = 0; i < 9; ++i)
+            if (!used[i] && (k < 0 || D[i] < D[k])) k = i;
+        used[k] = true;
+        for (int e = 0; e < 9; ++e) bs[3 - t][e] = V[e][k];
+    }
+    GeoModel cand[kEModels];
+    const int nc = e5_models<false>(bs, nullptr, nullptr, nullptr, nullptr, cand);
+    int best = -1;
+    double best_sum = 0.0;
+    for (int q = 0; q < nc; ++q) {
+        double sum = 0.0;
+        for (size_t i = 0; i < n; ++i)
+            sum += f_sq_sampson(c.x[idx[i]], c.y[idx[i]], c.a[idx[i]], c.c0[idx[i]], cand[q].h);
+        if (!(sum == sum)) continue;
+        if (best < 0 || sum < best_sum) { best = q; best_sum = sum; }
+    }
+    if (best < 0) return false;
+    out = cand[best];
+    return true;
+}
+
 }  // namespace gcr

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "ess.h"
 #include "fund.h"
 #include "geo.h"
 #include "gram.h"
@@ -88,6 +89,15 @@ bool fit_h4_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, Geo
 // (smallest eigenvector of A^T A by cyclic Jacobi, rank-2 projection), unit
 // Frobenius norm.  Blocked-order sums (qr3.h), restated by the oracle.
 bool fit_f8_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, GeoModel& out);
+
+// Non-minimal essential-matrix fit (LO and final refit; ess.h), on normalised
+// correspondences: exactly 5 points -> the 5-point solver's first model; more
+// -> the four eigenvectors of A^T A (rows in index order, sequential sums) with
+// the smallest eigenvalues by cyclic Jacobi, as W (smallest), Z, Y, X; ess.h's
+// steps 3-7 without the oriented test; of the up to kEModels candidates the
+// one with the smallest sum of squared Sampson residuals over the listed
+// points (sequential, the first on ties).
+bool fit_e5_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, GeoModel& out);
 
 // Cyclic Jacobi eigen-decomposition of a symmetric N x N matrix (a is
 // destroyed); eigenvalues d[k] with eigenvectors in the COLUMNS of v.

@@ -14,6 +14,7 @@
 // Compiled with -ffp-contract=off: every fp64 expression rounds exactly like
 // the host restatement.
 #include "kernels.h"
+#include "ess.h"
 #include "fm_groups.h"
 #include "guided.h"
 #include "philox.h"
@@ -235,6 +236,73 @@ __global__ __launch_bounds__(kGenBlock) void k_generate_f(DevProblem p, uint64_t
         for (int q = 0; q < kFModels; ++q) {
             models[(size_t)kFModels * s + q] = default_geo();
             inc[(size_t)kFModels * s + q] = q == 0 ? 102 : 255;
+        }
+    }
+}
+
+// Essential matrix: one attempt = Philox sample of 5 normalised
+// correspondences -> the 5-point solver (ess.h solve_e5, the host's function);
+// 0..kEModels models.  One lane per attempt: the 10 x 20 constraint matrix,
+// the derivative triangle of the root finder and the models are per-lane
+// arrays indexed at run time, which the compiler keeps in scratch memory.
+template <class DRAW>
+GCR_DEVICE int attempt_e(const DevProblem& p, uint64_t seed, uint64_t slot, uint32_t a, GeoModel* ms,
+                         const DRAW& dr) {
+    const DevClass& c = p.cls[0];
+    uint32_t idx[5];
+    WordStream ws(seed, slot, a, kStreamMain, 0);
+    if (!draw_sample<5>(ws, c.n, dr, idx)) return 0;
+    double x1[5], y1[5], x2[5], y2[5];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        x1[j] = c.x[idx[j]];
+        y1[j] = c.y[idx[j]];
+        x2[j] = c.a[idx[j]];
+        y2[j] = c.c0[idx[j]];
+    }
+    return solve_e5(x1, y1, x2, y2, ms);
+}
+
+// k_generate_f's layout with kEModels hypotheses per slot: fixed groups of G
+// lanes, round r tries attempts r G .. r G + G - 1, the lowest success wins.
+// inc[10 s] = attempt + 1 (102: all 101 attempts failed); inc[10 s + q],
+// q >= 1, = 0 if the q-th model exists and 255 if not; models packed to the
+// front in root order, the rest default_geo().
+template <int G, class... GT>
+__global__ __launch_bounds__(kGenBlock) void k_generate_e(DevProblem p, uint64_t seed, uint64_t slot0,
+                                                          uint32_t nslots, uint8_t* __restrict__ inc,
+                                                          GeoModel* __restrict__ models, GT... gt) {
+    static_assert(G >= 1 && G <= 64 && (64 % G) == 0, "group size");
+    const auto dr = stage_draw(gt...);
+    const uint32_t tid = blockIdx.x * kGenBlock + threadIdx.x;
+    const uint32_t s = tid / G;
+    const uint32_t g = tid % G;
+    if (s >= nslots) return;                 // whole groups exit together
+    const uint64_t slot = slot0 + s;
+    const int lane = threadIdx.x & 63;
+    const int gbase = lane & ~(G - 1);
+    GeoModel* out = models + (size_t)kEModels * s;
+    uint8_t* oi = inc + (size_t)kEModels * s;
+    for (uint32_t r = 0; r * G < 101; ++r) {
+        const uint32_t a = r * G + g;
+        GeoModel ms[kEModels];
+        const int cnt = a < 101 ? attempt_e(p, seed, slot, a, ms, dr) : 0;
+        const uint64_t mask = __ballot(cnt > 0);
+        const uint64_t grp = G == 64 ? mask : (mask >> gbase) & ((1ull << G) - 1ull);
+        if (grp) {
+            if (g == (uint32_t)__builtin_ctzll(grp)) {
+                for (int q = 0; q < kEModels; ++q) {
+                    out[q] = q < cnt ? ms[q] : default_geo();
+                    oi[q] = q == 0 ? (uint8_t)(a + 1) : (q < cnt ? 0 : 255);
+                }
+            }
+            return;
+        }
+    }
+    if (g == 0) {
+        for (int q = 0; q < kEModels; ++q) {
+            out[q] = default_geo();
+            oi[q] = q == 0 ? 102 : 255;
         }
     }
 }
@@ -5129,7 +5197,10 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
         // t: nothing (the uniform kernels) or the guided table
         auto run = [&](auto... t) {
-            if (p.solver == 4) {
+            if (p.solver == 5) {
+                hipLaunchKernelGGL((k_generate_e<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0, nslots,
+                                   inc, models, t...);
+            } else if (p.solver == 4) {
                 if (widen)
                     hipLaunchKernelGGL((k_generate_fw<4, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
                                        nslots, inc, models, t...);
@@ -5160,6 +5231,10 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
     // 8.08 / 7.77 / 7.38 / 7.43 ms
     int g = p.solver == 4 ? (nslots <= 8192 ? 16 : 8)
                           : (nslots <= 8192 ? 16 : nslots <= 32768 ? 4 : 1);
+    // 5-point solver: nearly every attempt yields a model (the solver's own
+    // rank tests and the oriented test are its only failures), so wide groups
+    // would mostly compute attempts that lose to attempt 0
+    if (p.solver == 5) g = nslots <= 32768 ? 4 : 1;
     if (env_g == 1 || env_g == 2 || env_g == 4 || env_g == 8 || env_g == 16 || env_g == 32 || env_g == 64) g = env_g;
     switch (g) {
         case 64: go(std::integral_constant<int, 64>{}); break;
@@ -5192,13 +5267,16 @@ __global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t
 hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
                                uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
     if (nslots == 0) return hipSuccess;
-    if (p.solver != 3 && p.solver != 4) return hipErrorInvalidValue;
+    if (p.solver != 3 && p.solver != 4 && p.solver != 5) return hipErrorInvalidValue;
     if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
                               (size_t)guided->stride * guided->buckets < guided->n))
         return hipErrorInvalidValue;
     const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
     auto run = [&](auto... t) {
-        if (p.solver == 4)
+        if (p.solver == 5)
+            hipLaunchKernelGGL((k_debug_sample<5, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
+                               nslots, attempt, out, t...);
+        else if (p.solver == 4)
             hipLaunchKernelGGL((k_debug_sample<7, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
                                nslots, attempt, out, t...);
         else
@@ -5366,7 +5444,7 @@ hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc,
                              uint32_t m, double Tm, BatchRecord* out, hipStream_t stream, const uint32_t* hmap,
                              const uint32_t* hcount) {
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(1), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
                        hcount);
     return hipGetLastError();
 }
@@ -5377,7 +5455,7 @@ hipError_t launch_select_geo_batches(int solver, const ScoreOut& sc, const uint8
     if (count == 0) return hipSuccess;
     if (stride < nh || stride == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(count), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
                        hcount, stride);
     return hipGetLastError();
 }

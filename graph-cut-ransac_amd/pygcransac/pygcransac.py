@@ -30,6 +30,7 @@ __all__ = [
     "findRectifyingHomographySIFT",
     "findHomography",
     "findFundamentalMatrix",
+    "findEssentialMatrix",
 ]
 
 _TWO_PI = 2.0 * math.pi
@@ -541,3 +542,46 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
                                 correspondences, h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 7, neighborhood_size, guided_stop)
+
+
+def _as_calibration(K, name):
+    k = np.ascontiguousarray(np.asarray(K, dtype=np.float64))
+    if k.shape != (3, 3):
+        raise ValueError(f"{name} must be a 3 x 3 calibration matrix; it has shape {tuple(k.shape)}.")
+    return k
+
+
+def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
+                        spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
+                        neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
+                        guided_stop=False):
+    """5-point essential matrix with graph-cut LO for calibrated cameras -- an
+    EXTENSION like findFundamentalMatrix (upstream pygcransac's
+    findEssentialMatrix order; csrc/ess.h is the solver's definition).
+
+    ``correspondences`` is (N, 4) float64 in PIXELS, ``K1`` and ``K2`` are the
+    3 x 3 calibration matrices (finite, third row exactly (0, 0, 1),
+    K[1, 0] == 0, positive focal lengths; skew allowed).  The estimator runs on
+    K^-1 x with the Sampson distance; ``threshold`` is in pixels and is divided
+    by the mean of the four focal lengths (upstream's rule).  The neighbourhood
+    grid lies over the pixel coordinates, as findFundamentalMatrix's.  A sample
+    yields up to ten models, each scored.  ``sampler``, ``probabilities`` (at
+    least 5 of them > 0) and ``guided_stop`` as in findHomography.
+
+    Returns ``(E, inliers)`` with E (3, 3), unit Frobenius norm and
+    (K2^-1 x2)^T E (K1^-1 x1) = 0, or ``(None, inliers)``.
+    """
+    k1 = _as_calibration(K1, "K1")
+    k2 = _as_calibration(K2, "K2")
+    # the engine's own check of the matrices, before any GPU work
+    N.check(N.lib.gcr_host_essential_normalise(None, 0, k1.ctypes.data, k2.ctypes.data, 0.0, None, None))
+
+    def entry(ctx, f, n, p, mask, M, st):
+        return N.lib.gcr_find_essential_matrix(ctx, f, n, k1.ctypes.data, k2.ctypes.data, None, p, mask, M, st)
+
+    def guided_entry(ctx, f, n, w, p, mask, M, st):
+        return N.lib.gcr_find_essential_matrix(ctx, f, n, k1.ctypes.data, k2.ctypes.data, w, p, mask, M, st)
+
+    return _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
+                                spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
+                                batch_slots, return_stats, 5, neighborhood_size, guided_stop)

@@ -178,3 +178,16 @@ def problem_f(n: int = 10_000, outlier_ratio: float = 0.8, seed: int = DEFAULT_S
     truth = np.concatenate([np.ones(n_in, bool), np.zeros(n_out, bool)])
     perm = rng.permutation(n)
     return np.ascontiguousarray(corr[perm]), truth[perm], F, 1.0
+
+
+def problem_e(n: int = 10_000, outlier_ratio: float = 0.8, seed: int = DEFAULT_SEED, noise: float = 0.5):
+    """Essential-matrix problem: problem_f's scene and pixel correspondences
+    with the calibration of two_view_geometry (both cameras).  Returns
+    correspondences (n, 4) in pixels, inlier truth mask, K, E_gt (normalised
+    coordinates: x^2^T E x^1 = 0 with x^ = K^-1 x, unit Frobenius norm) and the
+    inlier threshold (px)."""
+    corr, truth, _, thr = problem_f(n, outlier_ratio, seed, noise)
+    K, R, t, _ = two_view_geometry()
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    E = tx @ R
+    return corr, truth, K, E / np.linalg.norm(E), thr

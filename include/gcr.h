@@ -40,7 +40,8 @@ extern "C" {
  * new function, no struct changed size or layout, so the version stays 5.
  * The same holds for the guided stop: GCR_FLAG_GUIDED_STOP is a new bit of
  * gcr_params.flags (a call that leaves it clear runs as before), its host
- * and debug entries are new functions. */
+ * and debug entries are new functions.  The essential-matrix estimator
+ * (GCR_SOLVER_ESSENTIAL5) likewise: new functions and a new solver kind only. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -57,6 +58,8 @@ extern "C" {
 #define GCR_SOLVER_SIFT22 2          /* RectifyingHomographyTwoSIFTSolver           */
 #define GCR_SOLVER_HOMOGRAPHY4 3     /* 4-point homography (upstream GC-RANSAC)     */
 #define GCR_SOLVER_FUNDAMENTAL7 4    /* 7-point fundamental matrix (upstream)       */
+#define GCR_SOLVER_ESSENTIAL5 5      /* 5-point essential matrix (upstream); problems of
+                                        this kind come from gcr_problem_create_essential */
 
 typedef struct gcr_ctx gcr_ctx;
 typedef struct gcr_problem gcr_problem;
@@ -198,6 +201,23 @@ int gcr_find_fundamental_matrix_guided(gcr_ctx* ctx, const double* correspondenc
                                        const double* probabilities, const gcr_params* params, uint8_t* mask_out,
                                        double* F_out, gcr_stats* stats_out);
 
+/* 5-point essential matrix for calibrated cameras (an EXTENSION like the two
+ * above -- what upstream pygcransac's findEssentialMatrix would bind;
+ * csrc/ess.h is the definition).  correspondences: N x 4 PIXEL rows; K1, K2:
+ * row-major 3 x 3 calibration matrices, every entry finite, third row exactly
+ * (0, 0, 1), K[1][0] == 0, K[0][0] and K[1][1] > 0 (skew allowed); anything
+ * else, and n < 5, is GCR_EINVAL.  The estimator runs on x^ = K^-1 x (closed
+ * form, fp64) with the squared Sampson distance;
+ * params->scale_residual_thresh is in pixels and is divided by
+ * (K1[0][0] + K1[1][1] + K2[0][0] + K2[1][1]) / 4 (upstream's rule).  The
+ * neighbourhood grid of params (cell sizes in pixels) lies over the pixel
+ * rows.  probabilities: NULL = uniform sampling, else guided as in
+ * gcr_find_fundamental_matrix_guided (at least 5 weights > 0).  E_out:
+ * row-major 3 x 3, unit Frobenius norm, x^2^T E x^1 = 0. */
+int gcr_find_essential_matrix(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                              const double* K2, const double* probabilities, const gcr_params* params,
+                              uint8_t* mask_out, double* E_out, gcr_stats* stats_out);
+
 /* ---- batches of independent problems (SURVEY.md §8(b) gcr_rect_batch,
  * BASELINE configs[4]) ----------------------------------------------------- */
 typedef struct gcr_batch_item {
@@ -228,6 +248,15 @@ int gcr_solve_batch(int device, gcr_batch_item* items, size_t n, int concurrency
  * orientation set for GCR_SOLVER_SIFT22 and NULL otherwise. */
 int gcr_problem_create(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                        gcr_problem** out);
+/* A resident essential-matrix problem (GCR_SOLVER_ESSENTIAL5) from pixel
+ * rows and calibration matrices, checked as gcr_find_essential_matrix checks
+ * them.  gcr_problem_create(5, ...) carries no calibration and is GCR_EINVAL,
+ * as are essential items of gcr_solve_batch.  gcr_problem_run, _run_sharded,
+ * _run_comm, _verify_batch(es), _set_probabilities and the *_h debug hooks
+ * accept the problem; thresholds in their params are in pixels, models passed
+ * to or from the debug hooks are in normalised coordinates. */
+int gcr_problem_create_essential(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                                 const double* K2, gcr_problem** out);
 void gcr_problem_destroy(gcr_problem* prob);
 /* Guided sampling for a resident homography / fundamental-matrix problem (see
  * gcr_find_homography_guided): n must be the problem's N.  Everything that
@@ -340,12 +369,13 @@ int gcr_host_fit_nonminimal(int solver, const double* f0, size_t n0, const doubl
  * are 9 row-major doubles.  generate: homography -- inc[i] as above, H_out 9
  * per slot; fundamental -- 3 hypotheses per slot (inc_out 3 bytes, H_out 27
  * doubles per slot): inc[3s] as above, inc[3s+k] = 0 if the sample's k-th
- * model exists, 255 if not.  score: n0 / v0 / tot per model (MSAC threshold
+ * model exists, 255 if not; essential -- the same with 10 hypotheses per slot
+ * (inc_out 10 bytes, H_out 90 doubles per slot).  score: n0 / v0 / tot per model (MSAC threshold
  * 2.25 thr); mask: rules as gcr_debug_mask */
 int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc_out,
                          double* H_out);
-/* the generators' sampling function alone: the 4 / 7 indices of attempt
- * `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out: 4 / 7 per slot,
+/* the generators' sampling function alone: the 4 / 7 / 5 indices of attempt
+ * `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out: 4 / 7 / 5 per slot,
  * all-ones where the draw budget ran out), with the problem's sampler --
  * guided after gcr_problem_set_probabilities, else uniform */
 int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
@@ -358,7 +388,8 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
 /* host-only: the generators' validity check + minimal solver on the listed
  * rows (4: valid_sample_h4 + solve_h4; 7: solve_f7_basis + f7_model), in list
  * order, the functions the kernels call.  *count_out = 0 .. 3 models, 9
- * doubles each in models_out (room for 27). */
+ * doubles each in models_out (room for 27).  Solver 5: solve_e5 on NORMALISED
+ * rows, *count_out = 0 .. 10 models: models_out needs room for 90 doubles. */
 int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, const uint32_t* idx,
                            double* models_out, uint32_t* count_out);
 int gcr_debug_score_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels, uint32_t* n0,
@@ -376,6 +407,22 @@ int gcr_host_fit_h(const double* correspondences, size_t n, const uint32_t* idx,
 /* host-only: the fundamental-matrix LO / refit fit (7 points: 7-point solver's
  * first model; more: normalised 8-point with rank-2 projection) */
 int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* F_out);
+/* host-only: the essential-matrix LO / refit fit on NORMALISED rows (5 points:
+ * the 5-point solver's first model; more: the four smallest eigenvectors of
+ * A^T A through ess.h's steps 3-7, the candidate with the smallest Sampson
+ * sum) */
+int gcr_host_fit_e(const double* correspondences_normalised, size_t n, const uint32_t* idx, size_t k, double* E_out);
+/* host-only: the host twin of the essential-matrix generator with uniform
+ * draws, over `threads` host threads: gcr_debug_generate_h's inc_out (10 bytes
+ * per slot) and models (90 doubles per slot) of NORMALISED rows, bit for bit
+ * (measurements' CPU baseline; tests) */
+int gcr_host_generate_e(const double* correspondences_normalised, size_t n, uint64_t seed, uint64_t slot0,
+                        uint32_t nslots, int threads, uint8_t* inc_out, double* models_out);
+/* host-only: what an essential-matrix problem holds: normalised_out (N x 4) =
+ * the rows K-normalised, *threshold_out (may be NULL) = the pixel threshold
+ * in normalised units; K1 / K2 checked as gcr_find_essential_matrix does */
+int gcr_host_essential_normalise(const double* correspondences, size_t n, const double* K1, const double* K2,
+                                 double threshold, double* normalised_out, double* threshold_out);
 /* host-only: RectifyingHomography::getHomography (model.h:211-226), row-major */
 void gcr_host_homography(const gcr_rect_model* model, double* H_out);
 /* host-only: squared residuals of one rectification model over n features of
