@@ -566,6 +566,16 @@ void comm_sync(hipEvent_t ev, ncclComm_t comm, const char* what) {
 }
 }  // namespace
 
+// the calibrated estimators: K-normalised rows, pixel grid, pixel threshold
+static inline bool is_ess(int solver) {
+    return solver == GCR_SOLVER_ESSENTIAL5 || solver == GCR_SOLVER_ESSENTIAL3_GRAVITY;
+}
+
+// minimal sample size of a solver kind (6, gravity: 3, as 0 and 1)
+static inline size_t minimal_size(int solver) {
+    return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3;
+}
+
 struct gcr_problem {
     gcr_ctx* ctx = nullptr;
     int solver = 0;
@@ -600,6 +610,11 @@ struct gcr_problem {
     // to normalised coordinates.
     std::vector<double> pix[4];
     double thr_div = 1.0;
+    // Essential matrix with known gravity (solver 6): an essential problem plus
+    // the two gravity-alignment rotations, which the generator launches and
+    // the host fit get (grav.h)
+    GravRot rot{};
+    const GravRot* grav() const { return solver == GCR_SOLVER_ESSENTIAL3_GRAVITY ? &rot : nullptr; }
     // what the generator launches get: the problem's own solver kind
     DevProblem gen_dp() const {
         DevProblem d = dp;
@@ -608,13 +623,13 @@ struct gcr_problem {
     }
     // the residual threshold of params in the units of hc[0]
     double thr0(const gcr_params& prm) const {
-        return solver == GCR_SOLVER_ESSENTIAL5 ? prm.scale_residual_thresh / thr_div : prm.scale_residual_thresh;
+        return is_ess(solver) ? prm.scale_residual_thresh / thr_div : prm.scale_residual_thresh;
     }
 };
 
 // the correspondence estimators (GeoModel, N x 4 rows)
 static inline bool is_corr(int solver) {
-    return solver == GCR_SOLVER_HOMOGRAPHY4 || solver == GCR_SOLVER_FUNDAMENTAL7 || solver == GCR_SOLVER_ESSENTIAL5;
+    return solver == GCR_SOLVER_HOMOGRAPHY4 || solver == GCR_SOLVER_FUNDAMENTAL7 || is_ess(solver);
 }
 
 namespace {
@@ -1270,6 +1285,24 @@ int check_calibration(const double* K, const char* name) {
     return GCR_OK;
 }
 
+// A gravity-alignment rotation the gravity entries accept: row-major 3 x 3,
+// finite, |G G^T - I|_max <= 1e-9, det > 0
+int check_gravity(const double* G, const char* name) {
+    if (!G) return set_err(GCR_EINVAL, "%s: null rotation matrix", name);
+    for (int k = 0; k < 9; ++k)
+        if (!std::isfinite(G[k])) return set_err(GCR_EINVAL, "%s: entry %d is not finite", name, k);
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double d = (G[3 * r] * G[3 * c] + G[3 * r + 1] * G[3 * c + 1]) + G[3 * r + 2] * G[3 * c + 2];
+            if (!(std::fabs(d - (r == c ? 1.0 : 0.0)) <= 1e-9))
+                return set_err(GCR_EINVAL, "%s: not orthonormal (G G^T differs from I by more than 1e-9)", name);
+        }
+    const double det = (G[0] * (G[4] * G[8] - G[5] * G[7]) - G[1] * (G[3] * G[8] - G[5] * G[6])) +
+                       G[2] * (G[3] * G[7] - G[4] * G[6]);
+    if (!(det > 0.0)) return set_err(GCR_EINVAL, "%s: a reflection (determinant < 0), not a rotation", name);
+    return GCR_OK;
+}
+
 // x^ = K^-1 x in closed form: y^ = (y - cy) / fy, x^ = ((x - cx) - s y^) / fx
 inline void normalise_point(const double* K, double x, double y, double& xh, double& yh) {
     yh = (y - K[5]) / K[4];
@@ -1280,23 +1313,34 @@ inline void normalise_point(const double* K, double x, double y, double& xh, dou
 inline double essential_thr_div(const double* K1, const double* K2) { return (((K1[0] + K1[4]) + K2[0]) + K2[4]) / 4.0; }
 
 // K1 / K2 (both or neither): an essential-matrix problem (solver 5) from N x 4
-// pixel rows
+// pixel rows; with G1 / G2 as well: one with known gravity (solver 6)
 int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                  gcr_problem** out, bool shared_workspace = false, const double* K1 = nullptr,
-                 const double* K2 = nullptr) {
-    const bool ess = solver == GCR_SOLVER_ESSENTIAL5;
+                 const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr) {
+    const bool ess = is_ess(solver);
+    const bool grv = solver == GCR_SOLVER_ESSENTIAL3_GRAVITY;
+    if (grv && (K1 == nullptr || K2 == nullptr || G1 == nullptr || G2 == nullptr))
+        return set_err(GCR_EINVAL, "solver 6 (essential matrix with known gravity) needs the calibration matrices and "
+                                   "the gravity rotations: use gcr_problem_create_gravity_essential or "
+                                   "gcr_find_gravity_essential_matrix");
     if (ess && (K1 == nullptr || K2 == nullptr))
         return set_err(GCR_EINVAL, "solver 5 (essential matrix) needs the calibration matrices: use "
                                    "gcr_problem_create_essential or gcr_find_essential_matrix");
     if (!ctx || !out) return set_err(GCR_EINVAL, "null context or output pointer");
-    if (solver < 0 || solver > 5) return set_err(GCR_EINVAL, "unknown solver %d", solver);
+    if (solver < 0 || solver > 6) return set_err(GCR_EINVAL, "unknown solver %d", solver);
     const int K = solver == 2 ? 2 : 1;
-    const size_t m0 = solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3;
+    const size_t m0 = minimal_size(solver);
     if (!f0 || (K == 2 && !f1)) return set_err(GCR_EINVAL, "null feature pointer");
     if (ess) {
-        if (n0 < m0) return set_err(GCR_EINVAL, "an essential matrix needs at least 5 correspondences, got %zu", n0);
+        if (n0 < m0)
+            return set_err(GCR_EINVAL, "an essential matrix%s needs at least %zu correspondences, got %zu",
+                           grv ? " with known gravity" : "", m0, n0);
         if (int e = check_calibration(K1, "K1")) return e;
         if (int e = check_calibration(K2, "K2")) return e;
+    }
+    if (grv) {
+        if (int e = check_gravity(G1, "gravity_source")) return e;
+        if (int e = check_gravity(G2, "gravity_destination")) return e;
     }
     if (n0 < m0 || (K == 2 && n1 < 2))
         return set_err(GCR_EINTERNAL, "Data set smaller than minimal sample size for corresponding data type");
@@ -1319,6 +1363,11 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
         f0 = nrm.data();
         P->thr_div = essential_thr_div(K1, K2);
     }
+    if (grv)
+        for (int k = 0; k < 9; ++k) {
+            P->rot.g1[k] = G1[k];
+            P->rot.g2[k] = G2[k];
+        }
     // the host / device classes and the kernels' KIND: the fundamental matrix's
     const int dsolver = ess ? GCR_SOLVER_FUNDAMENTAL7 : solver;
     const size_t ns[2] = {n0, K == 2 ? n1 : 0};
@@ -1666,7 +1715,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static bool valid(int, const Model&) { return true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
-        return launch_generate_geo(P->gen_dp(), seed, s0, n, inc, m, s, P->guided());
+        return launch_generate_geo(P->gen_dp(), seed, s0, n, inc, m, s, P->guided(), P->grav());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1725,7 +1774,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     }
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
-        hipError_t e = launch_generate_geo(P->gen_dp(), seed, s0, n, b.inc, b.models, s, P->guided());
+        hipError_t e = launch_generate_geo(P->gen_dp(), seed, s0, n, b.inc, b.models, s, P->guided(), P->grav());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -1805,8 +1854,11 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
         return launch_score_geo(P->dp, T[0], m, inc, std::max<uint32_t>(live, 1u), out, s, P->w->hmap.p,
                                 P->w->hcount.p);
     }
-    static size_t per(gcr_problem* P) { return P->solver == 4 ? kFModels : P->solver == 5 ? kEModels : 1; }
+    static size_t per(gcr_problem* P) {
+        return P->solver == 4 ? kFModels : P->solver == 5 ? kEModels : P->solver == 6 ? kGModels : 1;
+    }
     static bool fit(gcr_problem* P, const std::vector<uint32_t>* lists, Model& out, bool) {
+        if (P->solver == 6) return fit_g3_nonminimal(P->hc[0], lists[0], P->rot, out);
         if (P->solver == 5) return fit_e5_nonminimal(P->hc[0], lists[0], out);
         if (P->solver == 4) return fit_f8_nonminimal(P->hc[0], lists[0], out);
         return fit_h4_nonminimal(P->hc[0], lists[0], out);
@@ -1830,6 +1882,10 @@ struct EssTraits : FundTraits {      // up to kEModels models per sample (ess.h)
     static constexpr size_t kPer = kEModels;
 };
 
+struct GravTraits : FundTraits {     // up to kGModels models per sample (grav.h)
+    static constexpr size_t kPer = kGModels;
+};
+
 constexpr int kMaxLOSample = 64;     // largest LO sample: 7 x the largest minimal sample (7)
 
 template <class Tr>
@@ -1843,7 +1899,7 @@ public:
     }
     RunnerT(gcr_problem* P, const gcr_params& prm) : P_(P), prm_(prm), s_(P->ctx->stream) {
         K_ = P->K;
-        m_[0] = P->solver == 2 ? 2 : P->solver == 3 ? 4 : P->solver == 4 ? 7 : P->solver == 5 ? 5 : 3;
+        m_[0] = minimal_size(P->solver);
         m_[1] = 2;
         thr_[0] = P->thr0(prm);
         thr_[1] = prm.orientation_residual_thresh;
@@ -3080,7 +3136,7 @@ private:
             if (P_->solver >= 3 && prm_.cell_number > 0 && prm_.spatial_coherence_weight > 0) {
                 const HostClass& c = P_->hc[0];
                 // essential matrix: the grid lies over the pixels
-                const bool px = P_->solver == GCR_SOLVER_ESSENTIAL5;
+                const bool px = is_ess(P_->solver);
                 const double* cols[4] = {px ? P_->pix[0].data() : c.x.data(), px ? P_->pix[1].data() : c.y.data(),
                                          px ? P_->pix[2].data() : c.a.data(), px ? P_->pix[3].data() : c.c0.data()};
                 // a cell size of 0 (image size unknown to the caller): the
@@ -4233,6 +4289,7 @@ using Runner = RunnerT<RectTraits>;
 using GeoRunner = RunnerT<GeoTraits>;
 using FundRunner = RunnerT<FundTraits>;
 using EssRunner = RunnerT<EssTraits>;
+using GravRunner = RunnerT<GravTraits>;
 
 }  // namespace
 
@@ -4315,14 +4372,12 @@ uint64_t build_quanta(const double* w, size_t n, double total, uint64_t* q) {
     return Q;
 }
 
-size_t minimal_size(int solver) { return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3; }
-
 // GCR_FLAG_GUIDED_STOP is valid only on a problem that samples guided
 int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
     if ((params->flags & GCR_FLAG_GUIDED_STOP) == 0) return GCR_OK;
     if (!is_corr(prob->solver))
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling exists for homography, "
-                                   "fundamental- and essential-matrix problems only");
+                                   "fundamental- and essential-matrix (5-point, gravity) problems only");
     if (prob->gt.cdf == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
                                    "(gcr_problem_set_probabilities)");
@@ -4512,6 +4567,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
             fill_stats(stats_out, r.stats());
             return total;
         };
+        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
         return prob->solver == GCR_SOLVER_HOMOGRAPHY4 ? go(GeoRunner(prob, *params)) : go(Runner(prob, *params));
@@ -4535,6 +4591,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
             fill_stats(stats_out, r.stats());
             return total;
         };
+        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
@@ -4614,6 +4671,7 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
             return total;
         };
         try {
+            if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
@@ -4647,6 +4705,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
             fill_stats(stats_out, r.stats());
             return GCR_OK;
         };
+        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
         return prob->solver == GCR_SOLVER_HOMOGRAPHY4 ? go(GeoRunner(prob, *params)) : go(Runner(prob, *params));
@@ -4662,7 +4721,7 @@ int gcr_problem_verify_batch(gcr_problem* prob, const gcr_params* params, uint64
 static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                        const gcr_params* params, uint8_t* m0, uint8_t* m1, double* H, gcr_rect_model* model,
                        gcr_stats* stats, const double* probabilities = nullptr, const double* K1 = nullptr,
-                       const double* K2 = nullptr) {
+                       const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr) {
     if (!ctx) return set_err(GCR_EINVAL, "null context");
     if (int e = check_params(params, solver)) return e;
     if ((params->flags & GCR_FLAG_GUIDED_STOP) != 0 && probabilities == nullptr)
@@ -4670,7 +4729,7 @@ static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, co
                                    "gcr_solve_batch's items carry no probabilities");
     const auto t0 = Clock::now();
     gcr_problem* prob = nullptr;
-    int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true, K1, K2); });
+    int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true, K1, K2, G1, G2); });
     if (rc != GCR_OK) return rc;
     if (probabilities != nullptr) rc = set_probabilities(prob, probabilities, n0);
     const double setup = ms_since(t0);
@@ -4893,6 +4952,132 @@ int gcr_host_fit_e(const double* correspondences, size_t n, const uint32_t* idx,
     });
 }
 
+// ---- essential matrix with known gravity (grav.h) -------------------------
+static bool load_rot(const double* G1, const double* G2, GravRot& rot) {
+    if (check_gravity(G1, "gravity_source") != GCR_OK || check_gravity(G2, "gravity_destination") != GCR_OK)
+        return false;
+    for (int k = 0; k < 9; ++k) {
+        rot.g1[k] = G1[k];
+        rot.g2[k] = G2[k];
+    }
+    return true;
+}
+
+int gcr_find_gravity_essential_matrix(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                                      const double* K2, const double* G1, const double* G2,
+                                      const double* probabilities, const gcr_params* params, uint8_t* mask_out,
+                                      double* E_out, gcr_stats* stats_out) {
+    if (!K1 || !K2) return set_err(GCR_EINVAL, "null calibration matrix");
+    if (int e = check_gravity(G1, "gravity_source")) return e;
+    if (int e = check_gravity(G2, "gravity_destination")) return e;
+    return run_oneshot(ctx, GCR_SOLVER_ESSENTIAL3_GRAVITY, correspondences, n, nullptr, 0, params, mask_out, nullptr,
+                       E_out, nullptr, stats_out, probabilities, K1, K2, G1, G2);
+}
+
+int gcr_problem_create_gravity_essential(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                                         const double* K2, const double* G1, const double* G2, gcr_problem** out) {
+    if (!K1 || !K2) return set_err(GCR_EINVAL, "null calibration matrix");
+    if (int e = check_gravity(G1, "gravity_source")) return e;
+    if (int e = check_gravity(G2, "gravity_destination")) return e;
+    return guard([&]() {
+        return make_problem(ctx, GCR_SOLVER_ESSENTIAL3_GRAVITY, correspondences, n, nullptr, 0, out, false, K1, K2, G1,
+                            G2);
+    });
+}
+
+int gcr_host_check_gravity(const double* G1, const double* G2) {
+    if (int e = check_gravity(G1, "gravity_source")) return e;
+    return check_gravity(G2, "gravity_destination");
+}
+
+int gcr_host_solve_g3(const double* correspondences, size_t n, const uint32_t* idx, const double* G1,
+                      const double* G2, double* models_out, uint32_t* count_out) {
+    if (!correspondences || !idx || !models_out || !count_out) return set_err(GCR_EINVAL, "null argument");
+    GravRot rot;
+    if (!load_rot(G1, G2, rot)) return GCR_EINVAL;
+    double x1[3], y1[3], x2[3], y2[3];
+    for (int j = 0; j < 3; ++j) {
+        if (idx[j] >= n) return set_err(GCR_EINVAL, "index out of range");
+        const double* r = correspondences + 4 * (size_t)idx[j];
+        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
+    }
+    // kernels.hip attempt_g: normalised rows, up to kGModels models
+    GeoModel ms[kGModels];
+    const int cnt = solve_g3(x1, y1, x2, y2, rot, ms);
+    for (int k = 0; k < cnt; ++k)
+        for (int q = 0; q < 9; ++q) models_out[9 * k + q] = ms[k].h[q];
+    *count_out = (uint32_t)cnt;
+    return GCR_OK;
+}
+
+int gcr_host_generate_g(const double* correspondences, size_t n, const double* G1, const double* G2,
+                        const double* probabilities, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
+                        uint8_t* inc_out, double* models_out) {
+    if (!correspondences || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
+    if (n < 3 || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
+    GravRot rot;
+    if (!load_rot(G1, G2, rot)) return GCR_EINVAL;
+    std::vector<double> tab;
+    GuidedTable gt{};
+    if (probabilities != nullptr)
+        if (int e = build_guided(probabilities, n, 3, tab, gt)) return e;
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    return guard([&]() -> int {
+        // k_generate_g's rule, slot by slot: attempts 0..100, the first success wins
+        auto work = [&](uint32_t lo, uint32_t hi) {
+            for (uint32_t s = lo; s < hi; ++s) {
+                uint8_t* oi = inc_out + (size_t)kGModels * s;
+                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)kGModels * s;
+                int cnt = 0;
+                uint32_t a = 0;
+                GeoModel ms[kGModels];
+                for (; a < 101 && cnt == 0; ++a) {
+                    uint32_t idx[3];
+                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
+                    const bool drawn = probabilities != nullptr ? sample_guided<3>(ws, gt, gt.coarse, 3, idx)
+                                                                : sample_distinct<3>(ws, n, 3, idx);
+                    if (!drawn) continue;
+                    double x1[3], y1[3], x2[3], y2[3];
+                    for (int j = 0; j < 3; ++j) {
+                        const double* r = correspondences + 4 * (size_t)idx[j];
+                        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
+                    }
+                    cnt = solve_g3(x1, y1, x2, y2, rot, ms);
+                }
+                for (int q = 0; q < kGModels; ++q) {
+                    out[q] = q < cnt ? ms[q] : default_geo();
+                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
+        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
+        work(0, std::min(nslots, step));
+        for (auto& t : pool) t.join();
+        return GCR_OK;
+    });
+}
+
+int gcr_host_fit_g(const double* correspondences, size_t n, const uint32_t* idx, size_t k, const double* G1,
+                   const double* G2, double* E_out) {
+    if (!correspondences || !idx || !E_out) return set_err(GCR_EINVAL, "bad arguments");
+    GravRot rot;
+    if (!load_rot(G1, G2, rot)) return GCR_EINVAL;
+    return guard([&]() -> int {
+        HostClass hc[2];
+        fill_host_classes(GCR_SOLVER_FUNDAMENTAL7, correspondences, n, nullptr, 0, hc);
+        std::vector<uint32_t> list(idx, idx + k);
+        for (uint32_t i : list)
+            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
+        GeoModel m;
+        if (!fit_g3_nonminimal(hc[0], list, rot, m)) return 0;
+        for (int q = 0; q < 9; ++q) E_out[q] = m.h[q];
+        return 1;
+    });
+}
+
 int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* F_out) {
     if (!correspondences || !idx || !F_out) return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
@@ -4921,7 +5106,8 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->inc.ensure(nh);
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
+        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided(),
+                                 prob->grav()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -4961,11 +5147,12 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
         // one untimed launch first (code object load, caches)
-        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided()));
+        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided(),
+                                 prob->grav()));
         HIPC(hipEventRecord(prob->ctx->ev0, s));
         for (int r = 0; r < reps; ++r)
             HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
-                                     prob->w->gmodels.p, s, prob->guided()));
+                                     prob->w->gmodels.p, s, prob->guided(), prob->grav()));
         HIPC(hipEventRecord(prob->ctx->ev1, s));
         HIPC(hipEventSynchronize(prob->ctx->ev1));
         float ms = 0.f;
@@ -4978,6 +5165,8 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
 int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, const uint32_t* idx,
                            double* models_out, uint32_t* count_out) {
     if (!correspondences || !idx || !models_out || !count_out) return set_err(GCR_EINVAL, "null argument");
+    if (solver == GCR_SOLVER_ESSENTIAL3_GRAVITY)
+        return set_err(GCR_EINVAL, "gcr_host_solve_minimal carries no gravity rotations: use gcr_host_solve_g3");
     if (!is_corr(solver))
         return set_err(GCR_EINVAL, "gcr_host_solve_minimal: homography, fundamental or essential matrix");
     const int m = (int)minimal_size(solver);

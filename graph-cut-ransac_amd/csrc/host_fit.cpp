@@ -515,6 +515,7 @@ void jacobi_eigen(double (&a)[N][N], double (&v)[N][N], double (&d)[N]) {
 }
 
 template void jacobi_eigen<3>(double (&)[3][3], double (&)[3][3], double (&)[3]);
+template void jacobi_eigen<6>(double (&)[6][6], double (&)[6][6], double (&)[6]);
 template void jacobi_eigen<9>(double (&)[9][9], double (&)[9][9], double (&)[9]);
 
 namespace {
@@ -685,6 +686,61 @@ bool fit_e5_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, Geo
     if (best < 0) return false;
     out = cand[best];
     return true;
+}
+
+bool fit_g3_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, const GravRot& rot, GeoModel& out) {
+    const size_t n = idx.size();
+    if (n < 3) return false;
+    if (n < 5) {
+        double x1[3], y1[3], x2[3], y2[3];
+        for (int i = 0; i < 3; ++i) {
+            x1[i] = c.x[idx[i]]; y1[i] = c.y[idx[i]]; x2[i] = c.a[idx[i]]; y2[i] = c.c0[idx[i]];
+        }
+        GeoModel ms[kGModels];
+        if (solve_g3(x1, y1, x2, y2, rot, ms) == 0) return false;
+        out = ms[0];
+        return true;
+    }
+    double ata[6][6] = {};
+    for (size_t i = 0; i < n; ++i) {
+        double p[3], q[3];
+        grav::align(rot.g1, c.x[idx[i]], c.y[idx[i]], p);
+        grav::align(rot.g2, c.a[idx[i]], c.c0[idx[i]], q);
+        const double r[6] = {q[0] * p[0] + q[2] * p[2], q[0] * p[1], q[0] * p[2] - q[2] * p[0],
+                             q[1] * p[0],               q[1] * p[2], q[2] * p[1]};
+        for (int u = 0; u < 6; ++u)
+            for (int v = u; v < 6; ++v) ata[u][v] += r[u] * r[v];
+    }
+    for (int u = 0; u < 6; ++u)
+        for (int v = 0; v < u; ++v) ata[u][v] = ata[v][u];
+    double V[6][6], D[6];
+    jacobi_eigen<6>(ata, V, D);
+    int k = 0;
+    for (int i = 1; i < 6; ++i)
+        if (D[i] < D[k]) k = i;
+    const double a = V[0][k], b = V[1][k], d = V[2][k], f = V[3][k], g = V[4][k], h = V[5][k];
+    const double tx0 = h, tz0 = -b;
+    const double nc = tz0 * f - tx0 * g, ns = tx0 * f + tz0 * g;
+    const double r2 = a * a + d * d, nn = sqrt(nc * nc + ns * ns);
+    // how far v itself can be trusted: lambda_min / lambda_next of A^T A
+    int k2 = k == 0 ? 1 : 0;
+    for (int i = 0; i < 6; ++i)
+        if (i != k && D[i] < D[k2]) k2 = i;
+    const double blur = D[k2] > 0.0 ? __builtin_fmax(D[k] / D[k2], 1e-12) : 1e-12;
+    double cs, sn;
+    if (r2 > blur || !(nn > 0.0)) {
+        const double r = sqrt(r2);
+        if (!(r > 0.0)) return false;
+        cs = d / r; sn = -a / r;
+        // the residual in (f, g) is a constant minus 2 (c nc + sn ns): the other sign where that is smaller
+        if (cs * nc + sn * ns < 0.0) { cs = -cs; sn = -sn; }
+    } else {
+        cs = nc / nn; sn = ns / nn;
+    }
+    const double ty = d * cs - a * sn;
+    const double tx = (tx0 + (sn * f - cs * g)) / 2.0;
+    const double tz = (tz0 + (cs * f + sn * g)) / 2.0;
+    return grav::compose(rot, tx, ty, tz, cs, sn, out.h);
 }
 
 }  // namespace gcr

@@ -15,6 +15,7 @@
 #include "fund.h"
 #include "geo.h"
 #include "gram.h"
+#include "grav.h"
 #include "rect.h"
 
 namespace gcr {
@@ -98,6 +99,31 @@ bool fit_f8_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, Geo
 // one with the smallest sum of squared Sampson residuals over the listed
 // points (sequential, the first on ties).
 bool fit_e5_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, GeoModel& out);
+
+// Non-minimal fit of the essential matrix with known gravity (LO and final
+// refit; grav.h), on normalised correspondences.  3 or 4 points -> the
+// 3-point solver's first model on the first three.  5 or more: in the aligned
+// frames E' = [[a, b, d], [f, 0, g], [-d, h, a]], so q^T E' p is linear in
+// v = (a, b, d, f, g, h) with the row (qx px + qz pz, qx py, qx pz - qz px,
+// qy px, qy pz, qz py); v = the eigenvector of A^T A (rows in index order,
+// sequential sums) with the smallest eigenvalue by cyclic Jacobi, the lowest
+// index on ties.  v is projected onto {[t]x R_y} by this rule:
+//   a = -ty sn, d = ty c, b = -tz, h = tx, f = tz c + tx sn, g = tz sn - tx c;
+//   tx0 = h, tz0 = -b, nc = tz0 f - tx0 g, ns = tx0 f + tz0 g
+//     (= (c, sn) (tx^2 + tz^2) on the set);
+//   ty and theta from (a, d): (c, sn) = (d, -a) / sqrt(a^2 + d^2), or its
+//     negative where that leaves the smaller residual in (f, g), which is
+//     where c nc + sn ns < 0;
+//   but where (a, d) is lost in v's own error, a^2 + d^2 <=
+//     max(lambda_min / lambda_next of A^T A, 1e-12) (no vertical translation,
+//     or one small against the noise: (a, d) carries no angle), theta from
+//     (b, f, g, h): (c, sn) = (nc, ns) over its norm, if that is > 0;
+//   a zero norm of whichever pair is used: no model;
+//   ty = d c - a sn, tx = (tx0 + (sn f - c g)) / 2, tz = (tz0 + (c f + sn g)) / 2
+//     (the least-squares t given the angle).
+// E = G2^T E' G1 at unit Frobenius norm by grav.h's step 7, without the
+// oriented test.  The returned model always has the constrained form.
+bool fit_g3_nonminimal(const HostClass& c, const std::vector<uint32_t>& idx, const GravRot& rot, GeoModel& out);
 
 // Cyclic Jacobi eigen-decomposition of a symmetric N x N matrix (a is
 // destroyed); eigenvalues d[k] with eigenvectors in the COLUMNS of v.

@@ -290,8 +290,13 @@ bool verify_chains(uint32_t nslots);
 // guided != nullptr: samples are drawn with the table's probabilities
 // (guided.h) by the generators' guided instantiations; the table goes to the
 // generator launches alone, DevProblem does not carry it.
+// solver 6 (essential matrix with known gravity, grav.h): kGModels hypotheses
+// per slot, and `grav` holds the two rotations (required for this solver,
+// nullptr for the others).
+struct GravRot;
 hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
-                               GeoModel* models, hipStream_t stream, const GuidedTable* guided = nullptr);
+                               GeoModel* models, hipStream_t stream, const GuidedTable* guided = nullptr,
+                               const GravRot* grav = nullptr);
 // The generators' sampling function alone (tests): the 4 / 7 indices of
 // attempt `attempt` of each slot into out, all-ones where the draw budget ran out.
 hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,

@@ -16,6 +16,7 @@
 #include "kernels.h"
 #include "ess.h"
 #include "fm_groups.h"
+#include "grav.h"
 #include "guided.h"
 #include "philox.h"
 #include "qr3.h"
@@ -301,6 +302,83 @@ __global__ __launch_bounds__(kGenBlock) void k_generate_e(DevProblem p, uint64_t
     }
     if (g == 0) {
         for (int q = 0; q < kEModels; ++q) {
+            out[q] = default_geo();
+            oi[q] = q == 0 ? 102 : 255;
+        }
+    }
+}
+
+// Essential matrix with known gravity: one attempt = Philox sample of 3
+// normalised correspondences -> the 3-point solver (grav.h solve_g3_slots, the
+// host's function); the models of the up to kGModels roots in fixed positions,
+// `valid` their bit mask.  Sample, polynomials and models are registers: no
+// array is indexed at run time.
+template <class DRAW>
+GCR_DEVICE unsigned attempt_g(const DevProblem& p, const GravRot& rot, uint64_t seed, uint64_t slot, uint32_t a,
+                              GeoModel (&ms)[kGModels], const DRAW& dr) {
+    const DevClass& c = p.cls[0];
+    uint32_t idx[3];
+    WordStream ws(seed, slot, a, kStreamMain, 0);
+    if (!draw_sample<3>(ws, c.n, dr, idx)) return 0;
+    double x1[3], y1[3], x2[3], y2[3];
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        x1[j] = c.x[idx[j]];
+        y1[j] = c.y[idx[j]];
+        x2[j] = c.a[idx[j]];
+        y2[j] = c.c0[idx[j]];
+    }
+    return solve_g3_slots(x1, y1, x2, y2, rot, ms);
+}
+
+// k_generate_e's layout with kGModels hypotheses per slot: fixed groups of G
+// lanes, round r tries attempts r G .. r G + G - 1, the lowest success wins.
+// inc[4 s] = attempt + 1 (102: all 101 attempts failed); inc[4 s + q],
+// q >= 1, = 0 if the q-th model exists and 255 if not; models packed to the
+// front in root order, the rest default_geo().  The rotations are a kernel
+// argument by value: wave-uniform.
+template <int G, class... GT>
+__global__ __launch_bounds__(kGenBlock) void k_generate_g(DevProblem p, GravRot rot, uint64_t seed, uint64_t slot0,
+                                                          uint32_t nslots, uint8_t* __restrict__ inc,
+                                                          GeoModel* __restrict__ models, GT... gt) {
+    static_assert(G >= 1 && G <= 64 && (64 % G) == 0, "group size");
+    const auto dr = stage_draw(gt...);
+    const uint32_t tid = blockIdx.x * kGenBlock + threadIdx.x;
+    const uint32_t s = tid / G;
+    const uint32_t g = tid % G;
+    if (s >= nslots) return;                 // whole groups exit together
+    const uint64_t slot = slot0 + s;
+    const int lane = threadIdx.x & 63;
+    const int gbase = lane & ~(G - 1);
+    GeoModel* out = models + (size_t)kGModels * s;
+    uint8_t* oi = inc + (size_t)kGModels * s;
+    for (uint32_t r = 0; r * G < 101; ++r) {
+        const uint32_t a = r * G + g;
+        GeoModel ms[kGModels];
+        const unsigned valid = a < 101 ? attempt_g(p, rot, seed, slot, a, ms, dr) : 0u;
+        const uint64_t mask = __ballot(valid != 0);
+        const uint64_t grp = G == 64 ? mask : (mask >> gbase) & ((1ull << G) - 1ull);
+        if (grp) {
+            if (g == (uint32_t)__builtin_ctzll(grp)) {
+                int k = 0;
+#pragma unroll
+                for (int t = 0; t < kGModels; ++t)
+                    if ((valid >> t) & 1u) {
+                        out[k] = ms[t];
+                        oi[k] = k == 0 ? (uint8_t)(a + 1) : 0;
+                        ++k;
+                    }
+                for (int q = k; q < kGModels; ++q) {
+                    out[q] = default_geo();
+                    oi[q] = 255;
+                }
+            }
+            return;
+        }
+    }
+    if (g == 0) {
+#pragma unroll
+        for (int q = 0; q < kGModels; ++q) {
             out[q] = default_geo();
             oi[q] = q == 0 ? 102 : 255;
         }
@@ -5179,8 +5257,10 @@ hipError_t launch_math(int op, const double* a, const double* b, size_t n, doubl
 
 // ------------------------------------ homography (3) / fundamental (4) ----
 hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
-                               GeoModel* models, hipStream_t stream, const GuidedTable* guided) {
+                               GeoModel* models, hipStream_t stream, const GuidedTable* guided,
+                               const GravRot* grav) {
     if (nslots == 0) return hipSuccess;
+    if ((p.solver == 6) != (grav != nullptr)) return hipErrorInvalidValue;
     if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
                               (size_t)guided->stride * guided->buckets < guided->n))
         return hipErrorInvalidValue;
@@ -5197,7 +5277,10 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
         // t: nothing (the uniform kernels) or the guided table
         auto run = [&](auto... t) {
-            if (p.solver == 5) {
+            if (p.solver == 6) {
+                hipLaunchKernelGGL((k_generate_g<G, decltype(t)...>), grid, block, 0, stream, p, *grav, seed, slot0,
+                                   nslots, inc, models, t...);
+            } else if (p.solver == 5) {
                 hipLaunchKernelGGL((k_generate_e<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0, nslots,
                                    inc, models, t...);
             } else if (p.solver == 4) {
@@ -5235,6 +5318,17 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
     // rank tests and the oriented test are its only failures), so wide groups
     // would mostly compute attempts that lose to attempt 0
     if (p.solver == 5) g = nslots <= 32768 ? 4 : 1;
+    // 3-point gravity solver: 1.34 attempts per slot at 80 % outliers (the
+    // oriented test and quartics without real roots fail the rest), yet a launch
+    // is bound by one wave's serial time (nine short bracket solves per attempt
+    // under divergence) times its rounds, so spare lanes pay as long as every
+    // wave is resident at once (2048 waves: 16 384 slots of 8 lanes).  Per
+    // launch of 1024 / 3712 / 14 848 / 65 536 slots: G = 1 -> 0.251 / 0.278 /
+    // 0.314 / 0.317 ms, 2 -> 0.146 / 0.162 / 0.184 / 0.209, 4 -> 0.091 / 0.097 /
+    // 0.110 / 0.207, 8 -> 0.062 / 0.066 / 0.085 / 0.273, 16 -> 0.062 / 0.067 /
+    // 0.140 / 0.507, 32 -> 0.065 / 0.079 / - / 0.978 (MEASUREMENTS.md; the
+    // choice made by reading the code before these numbers was 2)
+    if (p.solver == 6) g = nslots <= 16384 ? 8 : 4;
     if (env_g == 1 || env_g == 2 || env_g == 4 || env_g == 8 || env_g == 16 || env_g == 32 || env_g == 64) g = env_g;
     switch (g) {
         case 64: go(std::integral_constant<int, 64>{}); break;
@@ -5267,13 +5361,16 @@ __global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t
 hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
                                uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
     if (nslots == 0) return hipSuccess;
-    if (p.solver != 3 && p.solver != 4 && p.solver != 5) return hipErrorInvalidValue;
+    if (p.solver != 3 && p.solver != 4 && p.solver != 5 && p.solver != 6) return hipErrorInvalidValue;
     if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
                               (size_t)guided->stride * guided->buckets < guided->n))
         return hipErrorInvalidValue;
     const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
     auto run = [&](auto... t) {
-        if (p.solver == 5)
+        if (p.solver == 6)
+            hipLaunchKernelGGL((k_debug_sample<3, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
+                               nslots, attempt, out, t...);
+        else if (p.solver == 5)
             hipLaunchKernelGGL((k_debug_sample<5, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
                                nslots, attempt, out, t...);
         else if (p.solver == 4)
@@ -5444,7 +5541,7 @@ hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc,
                              uint32_t m, double Tm, BatchRecord* out, hipStream_t stream, const uint32_t* hmap,
                              const uint32_t* hcount) {
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(1), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
                        hcount);
     return hipGetLastError();
 }
@@ -5455,7 +5552,7 @@ hipError_t launch_select_geo_batches(int solver, const ScoreOut& sc, const uint8
     if (count == 0) return hipSuccess;
     if (stride < nh || stride == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(count), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
                        hcount, stride);
     return hipGetLastError();
 }

@@ -22,6 +22,7 @@ GCR_EINVAL = -22
 GCR_ENODEV = -19
 SOLVER_SCALE3, SOLVER_SCALE3_ORIGINAL, SOLVER_SIFT22, SOLVER_HOMOGRAPHY4, SOLVER_FUNDAMENTAL7 = 0, 1, 2, 3, 4
 SOLVER_ESSENTIAL5 = 5    # problems of this kind come from gcr_problem_create_essential
+SOLVER_ESSENTIAL3_GRAVITY = 6   # ... from gcr_problem_create_gravity_essential
 FLAG_NO_LO = 1
 FLAG_GUIDED_STOP = 2     # guided sampling only: the adaptive stop on the inlier mass (csrc/guided_stop.h)
 
@@ -219,6 +220,14 @@ def _load():
     L.gcr_host_fit_e.argtypes = L.gcr_host_fit_h.argtypes
     L.gcr_host_generate_e.argtypes = [vp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp, vp]
     L.gcr_host_essential_normalise.argtypes = [vp, C.c_size_t, vp, vp, C.c_double, vp, dp]
+    # essential matrix with known gravity (csrc/grav.h): ... + the two gravity-alignment rotations
+    L.gcr_find_gravity_essential_matrix.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, vp, C.POINTER(Params), vp, vp,
+                                                    C.POINTER(Stats)]
+    L.gcr_problem_create_gravity_essential.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, vp, C.POINTER(vp)]
+    L.gcr_host_check_gravity.argtypes = [vp, vp]
+    L.gcr_host_solve_g3.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, u32p]
+    L.gcr_host_fit_g.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
+    L.gcr_host_generate_g.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp, vp]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

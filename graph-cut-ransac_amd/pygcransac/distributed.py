@@ -235,7 +235,7 @@ class Comm:
 
 def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None, rank: int = 0, world: int = 1,
                         dist=None, device: Optional[int] = None, coll_device=None, comm: Optional[Comm] = None,
-                        probabilities=None, K1=None, K2=None):
+                        probabilities=None, K1=None, K2=None, G1=None, G2=None):
     """One estimator problem over `world` ranks.
 
     Every rank calls this with the same inputs; each verifies its block of
@@ -252,7 +252,8 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     exchanged records are the same).
     Solver 5 (essential matrix) takes pixel rows and the calibration matrices
     `K1`, `K2` (3 x 3); its threshold is in pixels and H is E in normalised
-    coordinates.
+    coordinates.  Solver 6 (essential matrix with known gravity) takes the
+    gravity-alignment rotations `G1`, `G2` (3 x 3) as well.
     Returns (H (3, 3) or None, masks tuple, stats dict, rect model record)."""
     import ctypes as C
 
@@ -263,13 +264,22 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     dp = lambda a: a.ctypes.data_as(C.POINTER(C.c_double))  # noqa: E731
     ctx = N.context(device)
     h = C.c_void_p()
-    if solver == N.SOLVER_ESSENTIAL5:
+    if solver in (N.SOLVER_ESSENTIAL5, N.SOLVER_ESSENTIAL3_GRAVITY):
         if K1 is None or K2 is None:
-            raise ValueError("solver 5 (essential matrix) needs K1 and K2")
+            raise ValueError(f"solver {solver} (essential matrix) needs K1 and K2")
         k1 = np.ascontiguousarray(K1, dtype=np.float64).reshape(3, 3)
         k2 = np.ascontiguousarray(K2, dtype=np.float64).reshape(3, 3)
-        N.check(N.lib.gcr_problem_create_essential(ctx, f0.ctypes.data, f0.shape[0], k1.ctypes.data, k2.ctypes.data,
-                                                   C.byref(h)))
+        if solver == N.SOLVER_ESSENTIAL5:
+            N.check(N.lib.gcr_problem_create_essential(ctx, f0.ctypes.data, f0.shape[0], k1.ctypes.data,
+                                                       k2.ctypes.data, C.byref(h)))
+        else:
+            if G1 is None or G2 is None:
+                raise ValueError("solver 6 (essential matrix with known gravity) needs G1 and G2")
+            g1 = np.ascontiguousarray(G1, dtype=np.float64).reshape(3, 3)
+            g2 = np.ascontiguousarray(G2, dtype=np.float64).reshape(3, 3)
+            N.check(N.lib.gcr_problem_create_gravity_essential(ctx, f0.ctypes.data, f0.shape[0], k1.ctypes.data,
+                                                               k2.ctypes.data, g1.ctypes.data, g2.ctypes.data,
+                                                               C.byref(h)))
     else:
         N.check(N.lib.gcr_problem_create(ctx, solver, dp(f0), f0.shape[0], dp(f1) if f1 is not None else None,
                                          0 if f1 is None else f1.shape[0], C.byref(h)))

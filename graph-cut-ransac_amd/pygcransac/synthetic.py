@@ -191,3 +191,57 @@ def problem_e(n: int = 10_000, outlier_ratio: float = 0.8, seed: int = DEFAULT_S
     tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
     E = tx @ R
     return corr, truth, K, E / np.linalg.norm(E), thr
+
+
+def gravity_geometry(seed: int = DEFAULT_SEED, focal: float = 1000.0):
+    """Calibration, gravity-alignment rotations and relative pose of a
+    two-view problem with known gravity: G1, G2 are seeded random rotations
+    (yaw, pitch, roll within +-0.15 rad: cameras held roughly upright), the
+    relative pose in the aligned frames is a rotation about y (+-0.3 rad) and
+    a unit translation.  Returns K, G1, G2, R, t (camera frames:
+    R = G2^T R_y G1, t = G2^T t') and E_gt = [t]x R at unit Frobenius norm."""
+    rng = np.random.default_rng([seed, 0x67726176])
+    K = np.array([[focal, 0, IMG_W / 2], [0, focal, IMG_H / 2], [0, 0, 1.0]])
+    G1 = _rot(*rng.uniform(-0.15, 0.15, 3))
+    G2 = _rot(*rng.uniform(-0.15, 0.15, 3))
+    th = rng.uniform(0.05, 0.3) * (1.0 if rng.uniform() < 0.5 else -1.0)
+    Ry = np.array([[math.cos(th), 0, math.sin(th)], [0, 1, 0], [-math.sin(th), 0, math.cos(th)]])
+    ta = np.array([1.0, rng.uniform(-0.3, 0.3), rng.uniform(-0.3, 0.3)])
+    ta /= np.linalg.norm(ta)
+    R = G2.T @ Ry @ G1
+    t = G2.T @ ta
+    tx = np.array([[0, -t[2], t[1]], [t[2], 0, -t[0]], [-t[1], t[0], 0]])
+    E = tx @ R
+    return K, G1, G2, R, t, E / np.linalg.norm(E)
+
+
+def problem_g(n: int = 10_000, outlier_ratio: float = 0.8, seed: int = DEFAULT_SEED, noise: float = 0.5):
+    """Essential-matrix problem with known gravity: problem_e's scene (the
+    same 3-D box, image size, calibration, noise and outliers; inlier
+    threshold 1 px) seen by the cameras of gravity_geometry(seed).  Returns
+    correspondences (n, 4) in pixels, inlier truth mask, K (both cameras),
+    G1, G2 and E_gt (normalised coordinates, unit Frobenius norm)."""
+    rng = np.random.default_rng(seed)
+    K, G1, G2, R, t, E = gravity_geometry(seed)
+    n_out = int(round(n * outlier_ratio))
+    n_in = n - n_out
+    pts = []
+    while sum(len(p) for p in pts) < n_in:
+        m = 2 * n_in + 8
+        X = np.stack([rng.uniform(-5, 5, m), rng.uniform(-4, 4, m), rng.uniform(6, 16, m)], axis=1)
+        p1 = X @ K.T
+        X2 = X @ R.T + t
+        p2 = X2 @ K.T
+        ok = (X2[:, 2] > 0.1)
+        u1, v1 = p1[:, 0] / p1[:, 2], p1[:, 1] / p1[:, 2]
+        u2, v2 = p2[:, 0] / p2[:, 2], p2[:, 1] / p2[:, 2]
+        ok &= (u1 >= 0) & (u1 < IMG_W) & (v1 >= 0) & (v1 < IMG_H) & (u2 >= 0) & (u2 < IMG_W) & (v2 >= 0) & (v2 < IMG_H)
+        pts.append(np.stack([u1, v1, u2, v2], axis=1)[ok])
+    inl = np.concatenate(pts)[:n_in]
+    inl = inl + rng.normal(0, noise, inl.shape)
+    out = np.stack([rng.uniform(0, IMG_W, n_out), rng.uniform(0, IMG_H, n_out),
+                    rng.uniform(0, IMG_W, n_out), rng.uniform(0, IMG_H, n_out)], axis=1)
+    corr = np.concatenate([inl, out])
+    truth = np.concatenate([np.ones(n_in, bool), np.zeros(n_out, bool)])
+    perm = rng.permutation(n)
+    return np.ascontiguousarray(corr[perm]), truth[perm], K, G1, G2, E

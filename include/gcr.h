@@ -41,7 +41,8 @@ extern "C" {
  * The same holds for the guided stop: GCR_FLAG_GUIDED_STOP is a new bit of
  * gcr_params.flags (a call that leaves it clear runs as before), its host
  * and debug entries are new functions.  The essential-matrix estimator
- * (GCR_SOLVER_ESSENTIAL5) likewise: new functions and a new solver kind only. */
+ * (GCR_SOLVER_ESSENTIAL5) likewise: new functions and a new solver kind only;
+ * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY). */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -60,6 +61,9 @@ extern "C" {
 #define GCR_SOLVER_FUNDAMENTAL7 4    /* 7-point fundamental matrix (upstream)       */
 #define GCR_SOLVER_ESSENTIAL5 5      /* 5-point essential matrix (upstream); problems of
                                         this kind come from gcr_problem_create_essential */
+#define GCR_SOLVER_ESSENTIAL3_GRAVITY 6 /* 3-point essential matrix with the gravity direction
+                                        of both cameras known; problems of this kind come
+                                        from gcr_problem_create_gravity_essential */
 
 typedef struct gcr_ctx gcr_ctx;
 typedef struct gcr_problem gcr_problem;
@@ -218,6 +222,25 @@ int gcr_find_essential_matrix(gcr_ctx* ctx, const double* correspondences, size_
                               const double* K2, const double* probabilities, const gcr_params* params,
                               uint8_t* mask_out, double* E_out, gcr_stats* stats_out);
 
+/* 3-point essential matrix for calibrated cameras whose gravity direction is
+ * known (an EXTENSION -- what upstream pygcransac's findGravityEssentialMatrix
+ * would bind; parity with upstream is unpinned, csrc/grav.h is the
+ * definition).  Everything as gcr_find_essential_matrix, plus G1
+ * (gravity_source) and G2 (gravity_destination): row-major 3 x 3 rotations,
+ * Gi taking a direction in camera i to a frame whose y axis is the gravity
+ * direction.  They must be finite with |G G^T - I|_max <= 1e-9 and det > 0;
+ * anything else is GCR_EINVAL with a message naming gravity_source or
+ * gravity_destination, before any GPU work.  n < 3 is GCR_EINVAL.  A sample
+ * is three correspondences and yields up to four models; probabilities need
+ * at least 3 weights > 0.  The relative rotation must not be a half turn about
+ * the vertical in the aligned frames (outside the solver's parametrisation).
+ * E_out: as gcr_find_essential_matrix's, in the ordinary normalised frames
+ * (x^2^T E x^1 = 0), of the form G2^T [t]x R_y G1. */
+int gcr_find_gravity_essential_matrix(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                                      const double* K2, const double* G1, const double* G2,
+                                      const double* probabilities, const gcr_params* params, uint8_t* mask_out,
+                                      double* E_out, gcr_stats* stats_out);
+
 /* ---- batches of independent problems (SURVEY.md §8(b) gcr_rect_batch,
  * BASELINE configs[4]) ----------------------------------------------------- */
 typedef struct gcr_batch_item {
@@ -257,6 +280,13 @@ int gcr_problem_create(gcr_ctx* ctx, int solver, const double* f0, size_t n0, co
  * to or from the debug hooks are in normalised coordinates. */
 int gcr_problem_create_essential(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
                                  const double* K2, gcr_problem** out);
+/* The same for the essential matrix with known gravity
+ * (GCR_SOLVER_ESSENTIAL3_GRAVITY): an essential problem plus the two rotations,
+ * checked as gcr_find_gravity_essential_matrix checks them.
+ * gcr_problem_create(6, ...) and items of gcr_solve_batch of kind 6 are
+ * GCR_EINVAL; everything the essential problem is accepted by accepts this one. */
+int gcr_problem_create_gravity_essential(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
+                                         const double* K2, const double* G1, const double* G2, gcr_problem** out);
 void gcr_problem_destroy(gcr_problem* prob);
 /* Guided sampling for a resident homography / fundamental-matrix problem (see
  * gcr_find_homography_guided): n must be the problem's N.  Everything that
@@ -370,12 +400,14 @@ int gcr_host_fit_nonminimal(int solver, const double* f0, size_t n0, const doubl
  * per slot; fundamental -- 3 hypotheses per slot (inc_out 3 bytes, H_out 27
  * doubles per slot): inc[3s] as above, inc[3s+k] = 0 if the sample's k-th
  * model exists, 255 if not; essential -- the same with 10 hypotheses per slot
- * (inc_out 10 bytes, H_out 90 doubles per slot).  score: n0 / v0 / tot per model (MSAC threshold
+ * (inc_out 10 bytes, H_out 90 doubles per slot), gravity essential with 4
+ * (4 bytes, 36 doubles).  score: n0 / v0 / tot per model (MSAC threshold
  * 2.25 thr); mask: rules as gcr_debug_mask */
 int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc_out,
                          double* H_out);
-/* the generators' sampling function alone: the 4 / 7 / 5 indices of attempt
- * `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out: 4 / 7 / 5 per slot,
+/* the generators' sampling function alone: the 4 / 7 / 5 / 3 (solvers 3 .. 6)
+ * indices of attempt `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out:
+ * as many per slot,
  * all-ones where the draw budget ran out), with the problem's sampler --
  * guided after gcr_problem_set_probabilities, else uniform */
 int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
@@ -423,6 +455,28 @@ int gcr_host_generate_e(const double* correspondences_normalised, size_t n, uint
  * in normalised units; K1 / K2 checked as gcr_find_essential_matrix does */
 int gcr_host_essential_normalise(const double* correspondences, size_t n, const double* K1, const double* K2,
                                  double threshold, double* normalised_out, double* threshold_out);
+/* host-only, essential matrix with known gravity (csrc/grav.h).  The rotations
+ * are checked as gcr_find_gravity_essential_matrix checks them.
+ * check_gravity: that check alone.
+ * solve_g3: the 3-point solver on the three listed NORMALISED rows
+ * (gcr_host_solve_minimal(6, ...) cannot carry the rotations and is
+ * GCR_EINVAL): *count_out = 0 .. 4 models in ascending root order, 9 doubles
+ * each, models_out needs room for 36.
+ * fit_g: the LO / refit fit (3 or 4 rows: the solver's first model; more: the
+ * constrained null vector, csrc/host_fit.h); returns 1 with E_out, 0 without a
+ * model.
+ * generate_g: the host twin of the generator, over `threads` host threads:
+ * gcr_debug_generate_h's inc_out (4 bytes per slot) and models (36 doubles per
+ * slot) bit for bit; probabilities NULL = uniform draws, else guided (n
+ * weights). */
+int gcr_host_check_gravity(const double* G1, const double* G2);
+int gcr_host_solve_g3(const double* correspondences_normalised, size_t n, const uint32_t* idx, const double* G1,
+                      const double* G2, double* models_out, uint32_t* count_out);
+int gcr_host_fit_g(const double* correspondences_normalised, size_t n, const uint32_t* idx, size_t k,
+                   const double* G1, const double* G2, double* E_out);
+int gcr_host_generate_g(const double* correspondences_normalised, size_t n, const double* G1, const double* G2,
+                        const double* probabilities, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
+                        uint8_t* inc_out, double* models_out);
 /* host-only: RectifyingHomography::getHomography (model.h:211-226), row-major */
 void gcr_host_homography(const gcr_rect_model* model, double* H_out);
 /* host-only: squared residuals of one rectification model over n features of
