@@ -1142,9 +1142,14 @@ __device__ __forceinline__ uint64_t realtime_now() {
 // survivors of a wave-round are appended hypothesis by hypothesis, each
 // hypothesis's entries in feature order.  The exact residuals of the
 // survivors are then evaluated with all 64 lanes busy, and the inlier values
-// -r^2 are packed by a running ballot prefix: hypothesis q's inlier values of
-// the wave-round are a contiguous run of outv[w], in feature order, delimited
-// by lohi[.][w][q], lohi[.][w][q + 1].
+// -r^2 go to slot k of the survivor's run: hypothesis q's values of the
+// wave-round are a contiguous run of outv[w], in feature order (+0.0 for a
+// survivor that is no inlier), zero-padded to whole chain batches; wcnt holds
+// the run's length.  The correspondence scorers give every hypothesis a fixed
+// region of outv[w]; the rectification scorers use outv[w] as a ring
+// (fm_groups.h): a wave-round's runs form one block sized by its survivors,
+// wcnt also holds each run's offset, and blocks of several rounds wait in the
+// ring for the chain wave.
 //
 // Wave 15 (the chain wave) folds the runs wave by wave and round by round:
 // exactly the inliers in feature order, which is the reference's sequential
@@ -1152,7 +1157,9 @@ __device__ __forceinline__ uint64_t realtime_now() {
 // +0.0 never changes it.  Outliers cost the chain nothing.  Waves hand over
 // through LDS flags instead of barriers (ready[w]: rounds published by wave
 // w; done[w]: rounds of wave w the chain has folded), so a compute wave only
-// waits when the chain still reads its previous run.
+// waits when the chain has not yet folded the runs it is about to overwrite:
+// its previous round's (fixed regions), or the newest round whose block the
+// new block overlaps (ring).
 // compile-time loop: f(std::integral_constant<int, Q>) for Q in [B, E)
 template <int B, int E, class F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -1188,6 +1195,14 @@ __device__ __forceinline__ void fm_wait_ge(const uint32_t* f, uint32_t v) {
 }
 __device__ __forceinline__ void fm_publish(uint32_t* f, uint32_t v) {
     __hip_atomic_store(f, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+// inclusive sum over each row of 16 lanes (DPP row shifts, 0 shifted in)
+__device__ __forceinline__ uint32_t fm_row_scan(uint32_t x) {
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xf, 0xf, true);   // row_shr:1
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xf, 0xf, true);   // row_shr:2
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xf, 0xf, true);   // row_shr:4
+    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xf, 0xf, true);   // row_shr:8
+    return x;
 }
 
 
@@ -1490,7 +1505,21 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
         kDyn ? reinterpret_cast<double2 (*)[H][kReg / 2]>(fm_dyn_lds) : outv_st;
     uint16_t (*const queue)[kQStride] =
         kDyn ? reinterpret_cast<uint16_t (*)[kQStride]>(fm_dyn_lds + (size_t)kW * H * (kReg / 2)) : queue_st;
-    __shared__ uint32_t wcnt[2][kW][H];                 // survivors of (wave, q) in the round
+    // The rectification scorers (KIND <= 2) use a wave's H regions as one
+    // value ring (fm_groups.h): a wave-round takes one contiguous block sized
+    // by its survivors, so a compute wave runs up to kWcD rounds ahead of the
+    // chain wave.  The correspondence scorers (64 VGPRs) keep the
+    // fixed regions, one round ahead.
+    constexpr bool kRing = KIND <= 2;
+    constexpr uint32_t kRingCap = (uint32_t)(H * kReg);
+    static_assert(!kRing || (H % 8 == 0 && 2 * kFmCB == (int)fmg::kRingRun),
+                  "value ring: blocks in whole chain batches of 16 doubles");
+    // rounds a wave may hold unfolded: the fused ring kRingDepth; the unfused
+    // one (15 compute waves) has LDS for 2 rows only, as the fixed regions
+    constexpr uint32_t kWcD = kRing && kGen ? fmg::kRingDepth : 2u;
+    // survivors of (wave, q) in the round, row fmg::ring_slot(gr, kWcD) (the
+    // fixed regions' fmg::round_parity); ring: n | offset << 16 (fmg::ring_pack)
+    __shared__ uint32_t wcnt[kWcD][kW][H];
     __shared__ uint32_t ready[kW], done[kW];
     using PairBand = std::conditional_t<KIND == 3, HPairBand, FPairBand>;
     static_assert(KIND >= 3 || (H & 1) == 0, "rectification pre-band: hypotheses in pairs");
@@ -1855,6 +1884,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
         double nxt[4];
         bool nok = false;
         if (rounds > 0) load(0, nxt, nok);
+        fmg::Ring ring;                                     // this wave's value ring (kRing), across the groups
       for (uint32_t g = 0; g < groups; ++g) {
         if (kGen && g > 0) {
             // group g's constants are in its set (the look-ahead wave);
@@ -1879,7 +1909,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             //    feature order) owns slot k of the region outv[wave][q], and
             //    the queue entry q | lane << 4 | k << 10 carries all of it
             uint32_t qn = 0, my_n = 0;
-            uint32_t* wc = wcnt[fmg::round_parity(gr)][wave];
+            uint32_t* wc = wcnt[fmg::ring_slot(gr, kWcD)][wave];
             // one fully unrolled hypothesis loop per band (the class is
             // uniform over a round): no class branch per q, the band itself
             // branch-free and evaluated on every lane (out-of-range lanes
@@ -2023,7 +2053,24 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 }
             }
             if (fm_probe(gen.probe, 2u)) qn = my_n = 0;
-            if (lane < H) wc[lane] = my_n;                 // survivors (run length) of (wave, q)
+            // survivors (run length) of (wave, q), and where the exact pass
+            // puts them: the fixed region q, free once the chain wave has
+            // folded the previous round, or (ring) lane q's run of the
+            // round's block, free once done[wave] >= need (fm_groups.h)
+            uint32_t need = gr > 0 ? fmg::region_free(gr) : 0u;
+            uint32_t roff = 0;                             // lane q: first double of run q
+            if constexpr (kRing) {
+                const uint32_t pn = fmg::ring_pad(my_n);
+                const uint32_t incl = fm_row_scan(pn);
+                const uint32_t size =
+                    fmg::ring_block((uint32_t)__builtin_amdgcn_readlane((int)incl, 15), (uint32_t)H);
+                const uint32_t base = fmg::ring_place(ring, size, kRingCap);
+                need = fmg::ring_wait(ring, gr, base, size, kWcD);
+                fmg::ring_commit(ring, base, size);
+                roff = base + (incl - pn) + fmg::ring_skew((uint32_t)lane);
+            } else {
+                if (lane < H) wc[lane] = my_n;
+            }
             GCR_STAMP(1, gr);
             // 2) + 3) exact residuals of the survivors, all 64 lanes busy: -r^2
             //    for an inlier, +0.0 (an exact no-op of the sum) otherwise.
@@ -2067,6 +2114,13 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     sv.a2 = fa2[fi];
                     if (KIND >= 3 || cls == 1) sv.a3 = fa3[fi];
                 }
+                if constexpr (kRing) {
+                    // the value's place in the ring, run offset from lane q:
+                    // the entry becomes q | (offset + k) << 4
+                    const uint32_t q = sv.e & 15u;
+                    const uint32_t o = (uint32_t)__builtin_amdgcn_ds_bpermute((int)(q << 2), (int)roff);
+                    sv.e = q | (o + (sv.e >> 10)) << 4;
+                }
 #ifdef GCR_FM_HQ_AHEAD
                 if constexpr (KIND <= 2) {
                     const HypConst& hq = cs->hyp[sv.e & 15u];
@@ -2090,8 +2144,13 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             const bool ahead = KIND < 3 && !fm_probe(gen.probe, 64u);     // (registers, see above)
             Surv cur{};
             if (ahead && qn > 0) cur = fetch(0);
-            // the chain has folded this wave's previous runs (outv reuse)
-            if (gr > 0 && !fm_probe(gen.probe, 256u)) fm_wait_ge(&done[wave], fmg::region_free(gr));
+            // the chain has folded this wave's previous runs (outv reuse); ring:
+            // the rounds whose blocks this round's block overlaps, and the
+            // round that used its wcnt row
+            if (need > 0 && !fm_probe(gen.probe, 256u)) fm_wait_ge(&done[wave], need);
+            if constexpr (kRing) {
+                if (lane < H) wc[lane] = fmg::ring_pack(my_n, roff);
+            }
             GCR_STAMP(2, gr);
             double* ow = reinterpret_cast<double*>(&outv[wave][0][0]);
             for (uint32_t j0 = 0; j0 < qn; j0 += 64) {
@@ -2100,7 +2159,8 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                 if (ahead && j0 + 64 < qn) nxt_s = fetch(j0 + 64);
                 const bool v = j0 + lane < qn;
                 const int q = (int)(cur.e & 15u);
-                const uint32_t k = cur.e >> 10;
+                // the value's double: slot k of region q, or its place in the ring
+                const uint32_t k = kRing ? cur.e >> 4 : (uint32_t)(q * kReg) + (cur.e >> 10);
                 if (v) {
                     const HypConst& hq = cs->hyp[q];
                     double r2;
@@ -2132,7 +2192,7 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                         }
 #endif
                     }
-                    ow[q * kReg + k] = inl ? -r2 : 0.0;
+                    ow[k] = inl ? -r2 : 0.0;
                     if (inl && !fm_probe(gen.probe, 512u)) atomicAdd(&cs->cnt[cls][q], 1u);
                     // a decision the host rechecks with glibc (exact.h); rare
                     if (KIND <= 2 && in_flag_band(r2, fl_mid, fl_half)) atomicAdd(&cs->fl[q], 1u);
@@ -2147,12 +2207,14 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
             // 4) zero-pad each run to a whole chain batch
             {
                 const int q = lane % H, part = lane / H;
-                const uint32_t n = wc[q];
+                const uint32_t wv = wc[q];
+                const uint32_t n = kRing ? fmg::ring_n(wv) : wv;
+                const uint32_t o = kRing ? fmg::ring_off(wv) : (uint32_t)(q * kReg);
                 const uint32_t end = (n + 2 * kFmCB - 1) & ~(uint32_t)(2 * kFmCB - 1);
 #pragma unroll
                 for (int i = 0; i < 2 * kFmCB * H / 64; ++i) {
                     const uint32_t s = n + part + i * (64 / H);
-                    if (s < end) ow[q * kReg + s] = 0.0;
+                    if (s < end) ow[o + s] = 0.0;
                 }
             }
             fm_publish(&ready[wave], fmg::published(gr));
@@ -2196,13 +2258,19 @@ __global__ __launch_bounds__(kSplitThreads) __attribute__((amdgpu_waves_per_eu(K
                     __builtin_amdgcn_s_sleep(1);
                     rmask = poll();
                 }
-                if (!have) n = wcnt[fmg::round_parity(gr)][w][h];
+                const uint32_t (*const wr)[H] = wcnt[fmg::ring_slot(gr, kWcD)];
+                if (!have) n = wr[w][h];
                 // the next run's length, read ahead if that wave has published
                 const bool nhave = w + 1 < kW && ((rmask >> (w + 1)) & 1ull);
-                const uint32_t nn = nhave ? wcnt[fmg::round_parity(gr)][w + 1][h] : 0u;
+                const uint32_t nn = nhave ? wr[w + 1][h] : 0u;
+                // ring: the word also carries the run's first double (even)
+                const double2* reg = outv[w][h];
+                if constexpr (kRing) {
+                    reg = &outv[w][0][0] + fmg::ring_off(n) / 2u;
+                    n = fmg::ring_n(n);
+                }
                 if (fold_on) {
                     // whole batches of kFmCB 16-byte reads (zero-padded runs)
-                    const double2* reg = outv[w][h];
                     // all of a batch's reads in flight before its adds, one
                     // batch at a time (a ping-pong variant with the next
                     // batch's reads in flight during the adds measured
