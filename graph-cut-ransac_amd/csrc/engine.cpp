@@ -5533,6 +5533,15 @@ int gcr_host_sample_guided(uint64_t seed, uint64_t index, uint32_t sub, uint32_t
                                                             : set_err(GCR_EINTERNAL, "sample budget exhausted");
 }
 
+int gcr_host_guided_index(const double* probabilities, size_t n, uint32_t m, uint64_t word, uint32_t* out) {
+    if (!out) return set_err(GCR_EINVAL, "null argument");
+    std::vector<double> tab;
+    GuidedTable t{};
+    if (int e = build_guided(probabilities, n, m, tab, t)) return e;
+    *out = guided_index(t, t.coarse, guided_u(word, t.total));
+    return GCR_OK;
+}
+
 int gcr_host_guided_quanta(const double* probabilities, size_t n, uint32_t m, uint64_t* q_out, uint64_t* Q_out) {
     if (!q_out || !Q_out) return set_err(GCR_EINVAL, "null argument");
     return guard([&]() -> int {

@@ -204,6 +204,7 @@ def _load():
     L.gcr_find_fundamental_matrix_guided.argtypes = L.gcr_find_homography_guided.argtypes
     L.gcr_host_sample_guided.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, vp, C.c_size_t,
                                          C.c_uint32, u32p]
+    L.gcr_host_guided_index.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_uint64, u32p]
     L.gcr_host_check_probabilities.argtypes = [vp, C.c_size_t, C.c_uint32]
     L.gcr_debug_sample_h.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, u32p]
     L.gcr_measure_generate_h.argtypes = [vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, dp]

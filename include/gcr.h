@@ -42,7 +42,8 @@ extern "C" {
  * gcr_params.flags (a call that leaves it clear runs as before), its host
  * and debug entries are new functions.  The essential-matrix estimator
  * (GCR_SOLVER_ESSENTIAL5) likewise: new functions and a new solver kind only;
- * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY). */
+ * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY), and the
+ * host hook gcr_host_guided_index. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -521,6 +522,10 @@ int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t
  * gcr_problem_set_probabilities checks them, with m as the minimal size */
 int gcr_host_sample_guided(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls,
                            const double* probabilities, size_t n, uint32_t m, uint32_t* out);
+/* host-only: the index one 64-bit word of the stream selects (the generators'
+ * two-level search, guided_index), weights checked as above: the draws no
+ * seed reaches in a test's time, such as word = 2^64 - 1 */
+int gcr_host_guided_index(const double* probabilities, size_t n, uint32_t m, uint64_t word, uint32_t* out);
 /* host-only: the guided stop's quanta (csrc/guided_stop.h) of raw weights,
  * checked as gcr_problem_set_probabilities checks them with m as the minimal
  * size: q_out[i] = (uint64_t)(w[i] / total * 2^(52 - bit_length(n))), *Q_out

@@ -409,3 +409,185 @@ def score_less(kind, f0, f1, ma, mb, thr0, thr1=0.0, math_mode=MATH_TWIN):
     r = L.oracle_score_less(kind, _dp(f0), f0.shape[0], _dp(f1) if f1 is not None else None,
                             0 if f1 is None else f1.shape[0], _dp(_f64(ma)), _dp(_f64(mb)), thr0, thr1, math_mode)
     return bool(r & 1), bool(r & 2), bool(r & 4)
+
+
+# ---------------------------------------- calibrated and guided whole runs ----
+_DP, _U32P, _U64P, _U8P = C.POINTER(C.c_double), C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.POINTER(C.c_uint8)
+MINIMAL_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _DP, C.c_size_t, _U32P, _DP)
+FIT_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, _DP, C.c_size_t, _U32P, C.c_size_t, _DP)
+_calib_ready = False
+
+
+def _calib_lib():
+    global _calib_ready
+    L = lib()
+    if not _calib_ready:
+        pp, sp = C.POINTER(OracleParams), C.POINTER(OracleStats)
+        L.oracle_find_calibrated.argtypes = [_DP, _DP, C.c_size_t, pp, C.c_uint32, C.c_uint32, MINIMAL_FN, FIT_FN,
+                                             C.c_void_p, _DP, C.c_int, _U8P, _DP, sp]
+        L.oracle_find_homography_guided.argtypes = [_DP, C.c_size_t, pp, _DP, C.c_int, _U8P, _DP, sp]
+        L.oracle_find_fundamental_guided.argtypes = L.oracle_find_homography_guided.argtypes
+        L.oracle_sample_guided.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _DP,
+                                           C.c_uint64, C.c_uint32, _U64P]
+        L.oracle_guided_pick.argtypes = [_DP, C.c_uint64, C.c_uint64]
+        L.oracle_guided_pick.restype = C.c_uint64
+        L.oracle_guided_quanta.argtypes = [_DP, C.c_uint64, _U64P, _U64P]
+        L.oracle_guided_quanta.restype = None
+        L.oracle_guided_iterations.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_double]
+        L.oracle_guided_iterations.restype = C.c_uint64
+        _calib_ready = True
+    return L
+
+
+def sample_guided(seed, index, sub, stream, cls, weights, m):
+    """One guided sample (the definition of csrc/guided.h restated): m distinct
+    indices in draw order, or None when the 4096-word budget runs out."""
+    w = _f64(weights)
+    out = np.zeros(m, dtype=np.uint64)
+    r = _calib_lib().oracle_sample_guided(seed, index, sub, stream, cls, _dp(w), len(w), m, out.ctypes.data_as(_U64P))
+    return out if r == 0 else None
+
+
+def guided_pick(weights, word):
+    """The index the 64-bit word `word` selects."""
+    w = _f64(weights)
+    return int(_calib_lib().oracle_guided_pick(_dp(w), len(w), word))
+
+
+def guided_quanta(weights):
+    """(q, Q) of csrc/guided_stop.h, restated."""
+    w = _f64(weights)
+    q = np.zeros(len(w), dtype=np.uint64)
+    Q = C.c_uint64()
+    _calib_lib().oracle_guided_quanta(_dp(w), len(w), q.ctypes.data_as(_U64P), C.byref(Q))
+    return q, Q.value
+
+
+def guided_iterations(mass, Q, m, confidence):
+    return int(_calib_lib().oracle_guided_iterations(mass, Q, m, confidence))
+
+
+def _weights(weights, n):
+    if weights is None:
+        return None
+    w = _f64(weights)
+    if w.shape != (n,):
+        raise ValueError("one weight per row")
+    return w
+
+
+def _guided_corr(entry, corr, thr, weights, guided_stop, kw):
+    c = _f64(corr)
+    n = c.shape[0]
+    w = _weights(weights, n)
+    mask = np.zeros(n, dtype=np.uint8)
+    M = np.zeros(9)
+    st = OracleStats()
+    p = params(thr, **kw)
+    r = entry(_dp(c), n, C.byref(p), None if w is None else _dp(w), int(bool(guided_stop)),
+              mask.ctypes.data_as(_U8P), _dp(M), C.byref(st))
+    if r < 0:
+        raise RuntimeError("oracle failed")
+    return dict(num_inliers=r, mask=mask.astype(bool), H=M.reshape(3, 3), stats=_stats_dict(st))
+
+
+def find_homography_guided(corr, thr, weights, guided_stop=False, **kw):
+    """find_homography with the main loop's samples drawn by the guided
+    sampler (weights None: the uniform run) and, with guided_stop, the stop on
+    the inlier mass."""
+    return _guided_corr(_calib_lib().oracle_find_homography_guided, corr, thr, weights, guided_stop, kw)
+
+
+def find_fundamental_guided(corr, thr, weights, guided_stop=False, **kw):
+    return _guided_corr(_calib_lib().oracle_find_fundamental_guided, corr, thr, weights, guided_stop, kw)
+
+
+def _guarded(fn):
+    """A callback that answers -1 (the oracle then fails the run) where fn
+    raises: ctypes would print the exception and return 0, "no model", and the
+    run would go on as a silently different one."""
+    def call(*args):
+        try:
+            return fn(*args)
+        except Exception:
+            import traceback
+
+            traceback.print_exc()
+            return -1
+
+    return call
+
+
+def _find_calibrated(corr, K1, K2, thr, m, per, minimal, fit, weights, guided_stop, image_size, neighborhood_size,
+                     kw):
+    """The oracle's run loop around the product's host solvers: rows and
+    threshold from gcr_host_essential_normalise, the grid over the pixels."""
+    from pygcransac import _native as N
+    from pygcransac import pygcransac as P
+
+    c = _f64(corr)
+    n = c.shape[0]
+    k1, k2 = _f64(K1), _f64(K2)
+    norm = np.zeros_like(c)
+    thr_n = C.c_double()
+    N.check(N.lib.gcr_host_essential_normalise(c.ctypes.data, n, k1.ctypes.data, k2.ctypes.data, float(thr),
+                                               norm.ctypes.data, C.byref(thr_n)))
+    if neighborhood_size:
+        kw = dict(kw, cell_size=P.grid_cell_sizes(c, *image_size, neighborhood_size), cell_number=neighborhood_size)
+    w = _weights(weights, n)
+    mask = np.zeros(n, dtype=np.uint8)
+    E = np.zeros(9)
+    st = OracleStats()
+    p = params(thr_n.value, **kw)
+    cb_min, cb_fit = MINIMAL_FN(_guarded(minimal)), FIT_FN(_guarded(fit))
+    r = _calib_lib().oracle_find_calibrated(_dp(norm), _dp(c), n, C.byref(p), m, per, cb_min, cb_fit, None,
+                                            None if w is None else _dp(w), int(bool(guided_stop)),
+                                            mask.ctypes.data_as(_U8P), _dp(E), C.byref(st))
+    if r < 0:
+        raise RuntimeError("oracle failed")
+    return dict(num_inliers=r, mask=mask.astype(bool), H=E.reshape(3, 3), stats=_stats_dict(st), rows=norm,
+                thr=thr_n.value)
+
+
+IMAGE_SIZE = (960.0, 1280.0, 960.0, 1280.0)          # h1, w1, h2, w2 of pygcransac.synthetic
+
+
+def find_essential(corr, K1, K2, thr, weights=None, guided_stop=False, image_size=IMAGE_SIZE, neighborhood_size=8,
+                   **kw):
+    """findEssentialMatrix through the oracle's run loop: the 5-point solver
+    and its fit reach it as callbacks over gcr_host_solve_minimal(5) and
+    gcr_host_fit_e.  thr in pixels.  Also returns the normalised rows and
+    threshold the run used ("rows", "thr")."""
+    from pygcransac import _native as N
+
+    cnt = C.c_uint32()
+
+    def minimal(user, rows, n, idx, out):
+        rc = N.lib.gcr_host_solve_minimal(N.SOLVER_ESSENTIAL5, rows, n, idx, out, C.byref(cnt))
+        return int(cnt.value) if rc == 0 else -1
+
+    def fit(user, rows, n, idx, k, out):
+        return N.lib.gcr_host_fit_e(rows, n, idx, k, out)
+
+    return _find_calibrated(corr, K1, K2, thr, 5, 10, minimal, fit, weights, guided_stop, image_size,
+                            neighborhood_size, kw)
+
+
+def find_gravity_essential(corr, K1, K2, G1, G2, thr, weights=None, guided_stop=False, image_size=IMAGE_SIZE,
+                           neighborhood_size=8, **kw):
+    """findGravityEssentialMatrix through the oracle's run loop, the callbacks
+    over gcr_host_solve_g3 and gcr_host_fit_g."""
+    from pygcransac import _native as N
+
+    g1, g2 = _f64(G1), _f64(G2)
+    cnt = C.c_uint32()
+
+    def minimal(user, rows, n, idx, out):
+        rc = N.lib.gcr_host_solve_g3(rows, n, idx, g1.ctypes.data, g2.ctypes.data, out, C.byref(cnt))
+        return int(cnt.value) if rc == 0 else -1
+
+    def fit(user, rows, n, idx, k, out):
+        return N.lib.gcr_host_fit_g(rows, n, idx, k, g1.ctypes.data, g2.ctypes.data, out)
+
+    return _find_calibrated(corr, K1, K2, thr, 3, 4, minimal, fit, weights, guided_stop, image_size,
+                            neighborhood_size, kw)
