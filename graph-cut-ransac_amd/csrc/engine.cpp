@@ -56,6 +56,7 @@
 #include "fm_groups.h"
 #include "philox.h"
 #include "qr3.h"
+#include "sifth.h"
 #include "graphcut.h"
 #include "host_pool.h"
 
@@ -571,9 +572,11 @@ static inline bool is_ess(int solver) {
     return solver == GCR_SOLVER_ESSENTIAL5 || solver == GCR_SOLVER_ESSENTIAL3_GRAVITY;
 }
 
-// minimal sample size of a solver kind (6, gravity: 3, as 0 and 1)
+// minimal sample size of a solver kind (6, gravity: 3, as 0 and 1; 7, SIFT
+// homography: 2)
 static inline size_t minimal_size(int solver) {
-    return solver == 2 ? 2 : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3;
+    return solver == 2 || solver == GCR_SOLVER_HOMOGRAPHY2_SIFT ? 2
+           : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3;
 }
 
 struct gcr_problem {
@@ -615,6 +618,13 @@ struct gcr_problem {
     // the host fit get (grav.h)
     GravRot rot{};
     const GravRot* grav() const { return solver == GCR_SOLVER_ESSENTIAL3_GRAVITY ? &rot : nullptr; }
+    // Homography from two SIFT correspondences (solver 7): a homography
+    // problem (dp.solver is 3: scoring, masks, residuals, the inlier mass and
+    // the non-minimal fit are the homography's) plus the stored SIFT columns
+    // (sifth.h), which live behind the classes in the workspace's feat and go
+    // to the generator launches alone
+    SiftCols scols{};
+    const SiftCols* sift() const { return solver == GCR_SOLVER_HOMOGRAPHY2_SIFT ? &scols : nullptr; }
     // what the generator launches get: the problem's own solver kind
     DevProblem gen_dp() const {
         DevProblem d = dp;
@@ -629,7 +639,8 @@ struct gcr_problem {
 
 // the correspondence estimators (GeoModel, N x 4 rows)
 static inline bool is_corr(int solver) {
-    return solver == GCR_SOLVER_HOMOGRAPHY4 || solver == GCR_SOLVER_FUNDAMENTAL7 || is_ess(solver);
+    return solver == GCR_SOLVER_HOMOGRAPHY4 || solver == GCR_SOLVER_FUNDAMENTAL7 || is_ess(solver) ||
+           solver == GCR_SOLVER_HOMOGRAPHY2_SIFT;
 }
 
 namespace {
@@ -1303,6 +1314,32 @@ int check_gravity(const double* G, const char* name) {
     return GCR_OK;
 }
 
+// The SIFT columns the SIFT homography entries accept, N x 4 rows (q1, q2,
+// alpha1, alpha2): sizes finite and > 0, orientations finite
+int check_sift(const double* sift, size_t n) {
+    if (!sift && n > 0) return set_err(GCR_EINVAL, "null SIFT columns");
+    static const char* const names[4] = {"q1", "q2", "alpha1", "alpha2"};
+    for (size_t i = 0; i < n; ++i)
+        for (int q = 0; q < 4; ++q) {
+            const double v = sift[4 * i + q];
+            if (!std::isfinite(v) || (q < 2 && !(v > 0.0)))
+                return set_err(GCR_EINVAL, "SIFT column %s, row %zu: %s", names[q], i,
+                               q < 2 ? "a feature size must be finite and > 0" : "an orientation must be finite");
+        }
+    return GCR_OK;
+}
+
+// sifth.h's stored columns of one row: (q2 / q1)^2 and the trig of both
+// orientations (glibc sincos, evaluated here once for host and device)
+inline void sift_row(const double* row, double out[5]) {
+    const double q = row[1] / row[0];
+    out[0] = q * q;
+    out[1] = std::cos(row[2]);
+    out[2] = std::sin(row[2]);
+    out[3] = std::cos(row[3]);
+    out[4] = std::sin(row[3]);
+}
+
 // x^ = K^-1 x in closed form: y^ = (y - cy) / fy, x^ = ((x - cx) - s y^) / fx
 inline void normalise_point(const double* K, double x, double y, double& xh, double& yh) {
     yh = (y - K[5]) / K[4];
@@ -1316,9 +1353,14 @@ inline double essential_thr_div(const double* K1, const double* K2) { return (((
 // pixel rows; with G1 / G2 as well: one with known gravity (solver 6)
 int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                  gcr_problem** out, bool shared_workspace = false, const double* K1 = nullptr,
-                 const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr) {
+                 const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr,
+                 const double* sift = nullptr) {
     const bool ess = is_ess(solver);
     const bool grv = solver == GCR_SOLVER_ESSENTIAL3_GRAVITY;
+    const bool sfh = solver == GCR_SOLVER_HOMOGRAPHY2_SIFT;
+    if (sfh && sift == nullptr)
+        return set_err(GCR_EINVAL, "solver 7 (homography from two SIFT correspondences) needs the SIFT columns: use "
+                                   "gcr_problem_create_sift_homography or gcr_find_homography_sift");
     if (grv && (K1 == nullptr || K2 == nullptr || G1 == nullptr || G2 == nullptr))
         return set_err(GCR_EINVAL, "solver 6 (essential matrix with known gravity) needs the calibration matrices and "
                                    "the gravity rotations: use gcr_problem_create_gravity_essential or "
@@ -1327,7 +1369,7 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
         return set_err(GCR_EINVAL, "solver 5 (essential matrix) needs the calibration matrices: use "
                                    "gcr_problem_create_essential or gcr_find_essential_matrix");
     if (!ctx || !out) return set_err(GCR_EINVAL, "null context or output pointer");
-    if (solver < 0 || solver > 6) return set_err(GCR_EINVAL, "unknown solver %d", solver);
+    if (solver < 0 || solver > 7) return set_err(GCR_EINVAL, "unknown solver %d", solver);
     const int K = solver == 2 ? 2 : 1;
     const size_t m0 = minimal_size(solver);
     if (!f0 || (K == 2 && !f1)) return set_err(GCR_EINVAL, "null feature pointer");
@@ -1341,6 +1383,12 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
     if (grv) {
         if (int e = check_gravity(G1, "gravity_source")) return e;
         if (int e = check_gravity(G2, "gravity_destination")) return e;
+    }
+    if (sfh) {
+        if (n0 < m0)
+            return set_err(GCR_EINVAL, "a homography from SIFT correspondences needs at least %zu of them, got %zu", m0,
+                           n0);
+        if (int e = check_sift(sift, n0)) return e;
     }
     if (n0 < m0 || (K == 2 && n1 < 2))
         return set_err(GCR_EINTERNAL, "Data set smaller than minimal sample size for corresponding data type");
@@ -1369,14 +1417,17 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
             P->rot.g2[k] = G2[k];
         }
     // the host / device classes and the kernels' KIND: the fundamental matrix's
-    const int dsolver = ess ? GCR_SOLVER_FUNDAMENTAL7 : solver;
+    // (the SIFT homography's: the homography's)
+    const int dsolver = ess ? GCR_SOLVER_FUNDAMENTAL7 : sfh ? GCR_SOLVER_HOMOGRAPHY4 : solver;
     const size_t ns[2] = {n0, K == 2 ? n1 : 0};
     std::vector<std::pair<const char*, Clock::time_point>> st;      // GCR_LO_TRACE: "gcr SETUP:"
     if (g_lo_trace) st.emplace_back("start", Clock::now());
     // SoA, every array padded to an even length (zeros) so that 16-byte
     // LDS-DMA strips (k_score_split staging) are aligned and in bounds
     const size_t np[2] = {(ns[0] + 1) & ~size_t(1), (ns[1] + 1) & ~size_t(1)};
-    const size_t total = 5 * (np[0] + np[1]);
+    // (solver 7: the five stored SIFT columns behind the classes)
+    const size_t soff = 5 * (np[0] + np[1]);
+    const size_t total = soff + (sfh ? 5 * np[0] : 0);
     HIPC(hipSetDevice(ctx->device));
     if (shared_workspace) {
         P->w = &ctx->shared;
@@ -1409,6 +1460,23 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
     const size_t off[2] = {0, 5 * np[0]};
     const FillOut fo = fill_host_classes(dsolver, f0, n0, f1, n1, P->hc, hst, np, off);
     if (solver <= 2) P->scales_ok = fo.scales_ok;
+    if (sfh) {
+        double* col = hst + soff;
+        // (the trig of 10 000 rows is 0.3 ms on one thread: in parts on the host pool, as the classes' fill)
+        const size_t parts = n0 >= 4096 ? 16 : 1;
+        const size_t step = (n0 + parts - 1) / parts;
+        host_pool().parallel_for(parts, [&](size_t q) {
+            for (size_t i = std::min(n0, q * step); i < std::min(n0, (q + 1) * step); ++i) {
+                double v[5];
+                sift_row(sift + 4 * i, v);
+                for (int k = 0; k < 5; ++k) col[(size_t)k * np[0] + i] = v[k];
+            }
+        });
+        for (int q = 0; q < 5; ++q)
+            for (size_t i = n0; i < np[0]; ++i) col[(size_t)q * np[0] + i] = 0.0;
+        const double* d = P->w->feat.p + soff;
+        P->scols = SiftCols{d, d + np[0], d + 2 * np[0], d + 3 * np[0], d + 4 * np[0]};
+    }
     if (g_lo_trace) st.emplace_back("fill", Clock::now());
     P->dp.solver = dsolver;
     for (int c = 0; c < 2; ++c) {
@@ -1715,7 +1783,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static bool valid(int, const Model&) { return true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
-        return launch_generate_geo(P->gen_dp(), seed, s0, n, inc, m, s, P->guided(), P->grav());
+        return launch_generate_geo(P->gen_dp(), seed, s0, n, inc, m, s, P->guided(), P->grav(), P->sift());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1774,7 +1842,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     }
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
-        hipError_t e = launch_generate_geo(P->gen_dp(), seed, s0, n, b.inc, b.models, s, P->guided(), P->grav());
+        hipError_t e = launch_generate_geo(P->gen_dp(), seed, s0, n, b.inc, b.models, s, P->guided(), P->grav(), P->sift());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -1855,7 +1923,8 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
                                 P->w->hcount.p);
     }
     static size_t per(gcr_problem* P) {
-        return P->solver == 4 ? kFModels : P->solver == 5 ? kEModels : P->solver == 6 ? kGModels : 1;
+        return P->solver == 4 ? kFModels : P->solver == 5 ? kEModels : P->solver == 6 ? kGModels
+               : P->solver == 7 ? kSModels : 1;
     }
     static bool fit(gcr_problem* P, const std::vector<uint32_t>* lists, Model& out, bool) {
         if (P->solver == 6) return fit_g3_nonminimal(P->hc[0], lists[0], P->rot, out);
@@ -1884,6 +1953,13 @@ struct EssTraits : FundTraits {      // up to kEModels models per sample (ess.h)
 
 struct GravTraits : FundTraits {     // up to kGModels models per sample (grav.h)
     static constexpr size_t kPer = kGModels;
+};
+
+// Homography from two SIFT correspondences: up to kSModels models per sample
+// (sifth.h), compacted as the fundamental matrix's are; P->dp.solver is 3, so
+// every scorer, mask and the fit are the homography's
+struct SiftHTraits : FundTraits {
+    static constexpr size_t kPer = kSModels;
 };
 
 constexpr int kMaxLOSample = 64;     // largest LO sample: 7 x the largest minimal sample (7)
@@ -4290,6 +4366,7 @@ using GeoRunner = RunnerT<GeoTraits>;
 using FundRunner = RunnerT<FundTraits>;
 using EssRunner = RunnerT<EssTraits>;
 using GravRunner = RunnerT<GravTraits>;
+using SiftHRunner = RunnerT<SiftHTraits>;
 
 }  // namespace
 
@@ -4377,13 +4454,23 @@ int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
     if ((params->flags & GCR_FLAG_GUIDED_STOP) == 0) return GCR_OK;
     if (!is_corr(prob->solver))
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling exists for homography, "
-                                   "fundamental- and essential-matrix (5-point, gravity) problems only");
+                                   "SIFT homography, fundamental- and essential-matrix (5-point, gravity) "
+                                   "problems only");
     if (prob->gt.cdf == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
                                    "(gcr_problem_set_probabilities)");
     if (prob->gQ == 0)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling's weights are too many and too small to "
                                    "measure (every share is below 2^-%d)", guided_quanta_shift(prob->hc[0].n));
+    return GCR_OK;
+}
+
+// a SIFT homography problem may hold 2 or 3 rows (generator tests); a run
+// fits and scores homographies, which takes 4
+int check_sift_rows(const gcr_problem* prob) {
+    if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT && prob->hc[0].n < 4)
+        return set_err(GCR_EINVAL, "a run of a SIFT homography problem needs at least 4 correspondences, got %zu",
+                       prob->hc[0].n);
     return GCR_OK;
 }
 
@@ -4559,6 +4646,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     if (int e = check_params(params, prob->solver)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
+    if (int e = check_sift_rows(prob)) return e;
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
@@ -4567,6 +4655,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
             fill_stats(stats_out, r.stats());
             return total;
         };
+        if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
@@ -4580,6 +4669,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     if (int e = check_params(params, prob->solver)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
+    if (int e = check_sift_rows(prob)) return e;
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allgather))
         return set_err(GCR_EINVAL, "bad rank/world/allgather");
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
@@ -4591,6 +4681,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
             fill_stats(stats_out, r.stats());
             return total;
         };
+        if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
@@ -4656,6 +4747,7 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
     if (comm->ctx != prob->ctx) return set_err(GCR_EINVAL, "communicator and problem on different contexts");
     if (int e = check_params(params, prob->solver)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
+    if (int e = check_sift_rows(prob)) return e;
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
     if (comm->aborted) return set_err(GCR_EINVAL, "communicator was aborted after an earlier error");
     return guard([&]() -> int {
@@ -4671,7 +4763,8 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
             return total;
         };
         try {
-            if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
+            if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
+        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
             if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
@@ -4697,6 +4790,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
     if (!prob || !out) return set_err(GCR_EINVAL, "null problem or output");
     if (int e = check_params(params, prob->solver)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
+    if (int e = check_sift_rows(prob)) return e;
     if (nslots == 0 || nbatches == 0) return set_err(GCR_EINVAL, "nslots and nbatches must be > 0");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
@@ -4705,6 +4799,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
             fill_stats(stats_out, r.stats());
             return GCR_OK;
         };
+        if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
         if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
@@ -4721,7 +4816,8 @@ int gcr_problem_verify_batch(gcr_problem* prob, const gcr_params* params, uint64
 static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const double* f1, size_t n1,
                        const gcr_params* params, uint8_t* m0, uint8_t* m1, double* H, gcr_rect_model* model,
                        gcr_stats* stats, const double* probabilities = nullptr, const double* K1 = nullptr,
-                       const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr) {
+                       const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr,
+                       const double* sift = nullptr) {
     if (!ctx) return set_err(GCR_EINVAL, "null context");
     if (int e = check_params(params, solver)) return e;
     if ((params->flags & GCR_FLAG_GUIDED_STOP) != 0 && probabilities == nullptr)
@@ -4729,7 +4825,7 @@ static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, co
                                    "gcr_solve_batch's items carry no probabilities");
     const auto t0 = Clock::now();
     gcr_problem* prob = nullptr;
-    int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true, K1, K2, G1, G2); });
+    int rc = guard([&]() { return make_problem(ctx, solver, f0, n0, f1, n1, &prob, true, K1, K2, G1, G2, sift); });
     if (rc != GCR_OK) return rc;
     if (probabilities != nullptr) rc = set_probabilities(prob, probabilities, n0);
     const double setup = ms_since(t0);
@@ -5078,6 +5174,106 @@ int gcr_host_fit_g(const double* correspondences, size_t n, const uint32_t* idx,
     });
 }
 
+// ---- homography from two SIFT correspondences (sifth.h) -------------------
+int gcr_find_homography_sift(gcr_ctx* ctx, const double* correspondences, const double* sift, size_t n,
+                             const double* probabilities, const gcr_params* params, uint8_t* mask_out, double* H_out,
+                             gcr_stats* stats_out) {
+    if (!sift) return set_err(GCR_EINVAL, "null SIFT columns");
+    if (n < 4)
+        return set_err(GCR_EINVAL, "gcr_find_homography_sift needs at least 4 correspondences, got %zu", n);
+    return run_oneshot(ctx, GCR_SOLVER_HOMOGRAPHY2_SIFT, correspondences, n, nullptr, 0, params, mask_out, nullptr,
+                       H_out, nullptr, stats_out, probabilities, nullptr, nullptr, nullptr, nullptr, sift);
+}
+
+int gcr_problem_create_sift_homography(gcr_ctx* ctx, const double* correspondences, const double* sift, size_t n,
+                                       gcr_problem** out) {
+    if (!sift) return set_err(GCR_EINVAL, "null SIFT columns");
+    return guard([&]() {
+        return make_problem(ctx, GCR_SOLVER_HOMOGRAPHY2_SIFT, correspondences, n, nullptr, 0, out, false, nullptr,
+                            nullptr, nullptr, nullptr, sift);
+    });
+}
+
+int gcr_host_check_sift(const double* sift, size_t n) { return check_sift(sift, n); }
+
+// rows idx[0], idx[1] as sifth.h's sample
+static void load_sift_sample(const double* correspondences, const double* sift, const uint32_t idx[2], double x1[2],
+                             double y1[2], double x2[2], double y2[2], SiftPair& sp) {
+    for (int j = 0; j < 2; ++j) {
+        const double* r = correspondences + 4 * (size_t)idx[j];
+        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
+        double v[5];
+        sift_row(sift + 4 * (size_t)idx[j], v);
+        sp.r[j] = v[0]; sp.c1[j] = v[1]; sp.s1[j] = v[2]; sp.c2[j] = v[3]; sp.s2[j] = v[4];
+    }
+}
+
+int gcr_host_solve_s2(const double* correspondences, const double* sift, size_t n, const uint32_t* idx,
+                      double* models_out, uint32_t* count_out) {
+    if (!correspondences || !sift || !idx || !models_out || !count_out) return set_err(GCR_EINVAL, "null argument");
+    for (int j = 0; j < 2; ++j) {
+        if (idx[j] >= n) return set_err(GCR_EINVAL, "index out of range");
+        if (int e = check_sift(sift + 4 * (size_t)idx[j], 1)) return e;
+    }
+    double x1[2], y1[2], x2[2], y2[2];
+    SiftPair sp;
+    load_sift_sample(correspondences, sift, idx, x1, y1, x2, y2, sp);
+    // kernels.hip attempt_s: up to kSModels models
+    GeoModel ms[kSModels];
+    const int cnt = solve_s2(x1, y1, x2, y2, sp, ms);
+    for (int k = 0; k < cnt; ++k)
+        for (int q = 0; q < 9; ++q) models_out[9 * k + q] = ms[k].h[q];
+    *count_out = (uint32_t)cnt;
+    return GCR_OK;
+}
+
+int gcr_host_generate_s(const double* correspondences, const double* sift, size_t n, const double* probabilities,
+                        uint64_t seed, uint64_t slot0, uint32_t nslots, int threads, uint8_t* inc_out,
+                        double* models_out) {
+    if (!correspondences || !sift || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
+    if (n < 2 || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
+    if (int e = check_sift(sift, n)) return e;
+    std::vector<double> tab;
+    GuidedTable gt{};
+    if (probabilities != nullptr)
+        if (int e = build_guided(probabilities, n, 2, tab, gt)) return e;
+    if (threads < 1) threads = 1;
+    if (threads > 256) threads = 256;
+    return guard([&]() -> int {
+        // k_generate_s's rule, slot by slot: attempts 0..100, the first success wins
+        auto work = [&](uint32_t lo, uint32_t hi) {
+            for (uint32_t s = lo; s < hi; ++s) {
+                uint8_t* oi = inc_out + (size_t)kSModels * s;
+                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)kSModels * s;
+                int cnt = 0;
+                uint32_t a = 0;
+                GeoModel ms[kSModels];
+                for (; a < 101 && cnt == 0; ++a) {
+                    uint32_t idx[2];
+                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
+                    const bool drawn = probabilities != nullptr ? sample_guided<2>(ws, gt, gt.coarse, 2, idx)
+                                                                : sample_distinct<2>(ws, n, 2, idx);
+                    if (!drawn) continue;
+                    double x1[2], y1[2], x2[2], y2[2];
+                    SiftPair sp;
+                    load_sift_sample(correspondences, sift, idx, x1, y1, x2, y2, sp);
+                    cnt = solve_s2(x1, y1, x2, y2, sp, ms);
+                }
+                for (int q = 0; q < kSModels; ++q) {
+                    out[q] = q < cnt ? ms[q] : default_geo();
+                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
+        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
+        work(0, std::min(nslots, step));
+        for (auto& t : pool) t.join();
+        return GCR_OK;
+    });
+}
+
 int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* F_out) {
     if (!correspondences || !idx || !F_out) return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
@@ -5107,7 +5303,7 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
         HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided(),
-                                 prob->grav()));
+                                 prob->grav(), prob->sift()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -5148,11 +5344,11 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
         hipStream_t s = prob->ctx->stream;
         // one untimed launch first (code object load, caches)
         HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided(),
-                                 prob->grav()));
+                                 prob->grav(), prob->sift()));
         HIPC(hipEventRecord(prob->ctx->ev0, s));
         for (int r = 0; r < reps; ++r)
             HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
-                                     prob->w->gmodels.p, s, prob->guided(), prob->grav()));
+                                     prob->w->gmodels.p, s, prob->guided(), prob->grav(), prob->sift()));
         HIPC(hipEventRecord(prob->ctx->ev1, s));
         HIPC(hipEventSynchronize(prob->ctx->ev1));
         float ms = 0.f;
@@ -5167,6 +5363,8 @@ int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, 
     if (!correspondences || !idx || !models_out || !count_out) return set_err(GCR_EINVAL, "null argument");
     if (solver == GCR_SOLVER_ESSENTIAL3_GRAVITY)
         return set_err(GCR_EINVAL, "gcr_host_solve_minimal carries no gravity rotations: use gcr_host_solve_g3");
+    if (solver == GCR_SOLVER_HOMOGRAPHY2_SIFT)
+        return set_err(GCR_EINVAL, "gcr_host_solve_minimal carries no SIFT columns: use gcr_host_solve_s2");
     if (!is_corr(solver))
         return set_err(GCR_EINVAL, "gcr_host_solve_minimal: homography, fundamental or essential matrix");
     const int m = (int)minimal_size(solver);

@@ -293,10 +293,15 @@ bool verify_chains(uint32_t nslots);
 // solver 6 (essential matrix with known gravity, grav.h): kGModels hypotheses
 // per slot, and `grav` holds the two rotations (required for this solver,
 // nullptr for the others).
+// solver 7 (homography from two SIFT correspondences, sifth.h): kSModels
+// hypotheses per slot, and `sift` holds the device pointers of the stored SIFT
+// columns (required for this solver, nullptr for the others); p's classes,
+// scorers and masks are the homography's.
 struct GravRot;
+struct SiftCols;
 hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
                                GeoModel* models, hipStream_t stream, const GuidedTable* guided = nullptr,
-                               const GravRot* grav = nullptr);
+                               const GravRot* grav = nullptr, const SiftCols* sift = nullptr);
 // The generators' sampling function alone (tests): the 4 / 7 indices of
 // attempt `attempt` of each slot into out, all-ones where the draw budget ran out.
 hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,

@@ -20,6 +20,7 @@
 #include "guided.h"
 #include "philox.h"
 #include "qr3.h"
+#include "sifth.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -379,6 +380,89 @@ __global__ __launch_bounds__(kGenBlock) void k_generate_g(DevProblem p, GravRot 
     if (g == 0) {
 #pragma unroll
         for (int q = 0; q < kGModels; ++q) {
+            out[q] = default_geo();
+            oi[q] = q == 0 ? 102 : 255;
+        }
+    }
+}
+
+// Homography from two SIFT correspondences: one attempt = Philox sample of 2
+// correspondences and their stored SIFT columns -> the 2-point solver (sifth.h
+// solve_s2_slots, the host's function); the models of the up to kSModels roots
+// in fixed positions, `valid` their bit mask.  Sample, elimination, cubic and
+// models are registers: no array is indexed at run time.
+template <class DRAW>
+GCR_DEVICE unsigned attempt_s(const DevProblem& p, const SiftCols& sc, uint64_t seed, uint64_t slot, uint32_t a,
+                              GeoModel (&ms)[kSModels], const DRAW& dr) {
+    const DevClass& c = p.cls[0];
+    uint32_t idx[2];
+    WordStream ws(seed, slot, a, kStreamMain, 0);
+    if (!draw_sample<2>(ws, c.n, dr, idx)) return 0;
+    double x1[2], y1[2], x2[2], y2[2];
+    SiftPair sp;
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        x1[j] = c.x[idx[j]];
+        y1[j] = c.y[idx[j]];
+        x2[j] = c.a[idx[j]];
+        y2[j] = c.c0[idx[j]];
+        sp.r[j] = sc.r[idx[j]];
+        sp.c1[j] = sc.c1[idx[j]];
+        sp.s1[j] = sc.s1[idx[j]];
+        sp.c2[j] = sc.c2[idx[j]];
+        sp.s2[j] = sc.s2[idx[j]];
+    }
+    return solve_s2_slots(x1, y1, x2, y2, sp, ms);
+}
+
+// k_generate_g's layout with kSModels hypotheses per slot: fixed groups of G
+// lanes, round r tries attempts r G .. r G + G - 1, the lowest success wins.
+// inc[3 s] = attempt + 1 (102: all 101 attempts failed); inc[3 s + q],
+// q >= 1, = 0 if the q-th model exists and 255 if not; models packed to the
+// front in root order, the rest default_geo().  The column pointers are a
+// kernel argument by value: wave-uniform.
+template <int G, class... GT>
+__global__ __launch_bounds__(kGenBlock) void k_generate_s(DevProblem p, SiftCols sc, uint64_t seed, uint64_t slot0,
+                                                          uint32_t nslots, uint8_t* __restrict__ inc,
+                                                          GeoModel* __restrict__ models, GT... gt) {
+    static_assert(G >= 1 && G <= 64 && (64 % G) == 0, "group size");
+    const auto dr = stage_draw(gt...);
+    const uint32_t tid = blockIdx.x * kGenBlock + threadIdx.x;
+    const uint32_t s = tid / G;
+    const uint32_t g = tid % G;
+    if (s >= nslots) return;                 // whole groups exit together
+    const uint64_t slot = slot0 + s;
+    const int lane = threadIdx.x & 63;
+    const int gbase = lane & ~(G - 1);
+    GeoModel* out = models + (size_t)kSModels * s;
+    uint8_t* oi = inc + (size_t)kSModels * s;
+    for (uint32_t r = 0; r * G < 101; ++r) {
+        const uint32_t a = r * G + g;
+        GeoModel ms[kSModels];
+        const unsigned valid = a < 101 ? attempt_s(p, sc, seed, slot, a, ms, dr) : 0u;
+        const uint64_t mask = __ballot(valid != 0);
+        const uint64_t grp = G == 64 ? mask : (mask >> gbase) & ((1ull << G) - 1ull);
+        if (grp) {
+            if (g == (uint32_t)__builtin_ctzll(grp)) {
+                int k = 0;
+#pragma unroll
+                for (int t = 0; t < kSModels; ++t)
+                    if ((valid >> t) & 1u) {
+                        out[k] = ms[t];
+                        oi[k] = k == 0 ? (uint8_t)(a + 1) : 0;
+                        ++k;
+                    }
+                for (int q = k; q < kSModels; ++q) {
+                    out[q] = default_geo();
+                    oi[q] = 255;
+                }
+            }
+            return;
+        }
+    }
+    if (g == 0) {
+#pragma unroll
+        for (int q = 0; q < kSModels; ++q) {
             out[q] = default_geo();
             oi[q] = q == 0 ? 102 : 255;
         }
@@ -5326,9 +5410,10 @@ hipError_t launch_math(int op, const double* a, const double* b, size_t n, doubl
 // ------------------------------------ homography (3) / fundamental (4) ----
 hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
                                GeoModel* models, hipStream_t stream, const GuidedTable* guided,
-                               const GravRot* grav) {
+                               const GravRot* grav, const SiftCols* sift) {
     if (nslots == 0) return hipSuccess;
     if ((p.solver == 6) != (grav != nullptr)) return hipErrorInvalidValue;
+    if ((p.solver == 7) != (sift != nullptr)) return hipErrorInvalidValue;
     if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
                               (size_t)guided->stride * guided->buckets < guided->n))
         return hipErrorInvalidValue;
@@ -5345,7 +5430,10 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
         // t: nothing (the uniform kernels) or the guided table
         auto run = [&](auto... t) {
-            if (p.solver == 6) {
+            if (p.solver == 7) {
+                hipLaunchKernelGGL((k_generate_s<G, decltype(t)...>), grid, block, 0, stream, p, *sift, seed, slot0,
+                                   nslots, inc, models, t...);
+            } else if (p.solver == 6) {
                 hipLaunchKernelGGL((k_generate_g<G, decltype(t)...>), grid, block, 0, stream, p, *grav, seed, slot0,
                                    nslots, inc, models, t...);
             } else if (p.solver == 5) {
@@ -5397,6 +5485,18 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
     // 0.140 / 0.507, 32 -> 0.065 / 0.079 / - / 0.978 (MEASUREMENTS.md; the
     // choice made by reading the code before these numbers was 2)
     if (p.solver == 6) g = nslots <= 16384 ? 8 : 4;
+    // 2-point SIFT homography solver: 3.3 attempts per slot at 80 % outliers
+    // (3.9 at 95 %: a cubic always has a real root, the failures are the sign
+    // and orientation tests on outlier pairs), each attempt one long serial
+    // chain (the 6 x 9 elimination, the bracket solves), so spare lanes pay
+    // while the waves are resident at once.  Per launch of 1024 / 3712 /
+    // 14 848 / 65 536 slots at 80 % outliers: G = 1 -> 0.466 / 0.520 / 0.571 /
+    // 0.590 ms, 2 -> 0.251 / 0.286 / 0.299 / 0.382, 4 -> 0.142 / 0.152 / 0.162 /
+    // 0.312, 8 -> 0.088 / 0.090 / 0.117 / 0.290, 16 -> 0.052 / 0.056 / 0.109 /
+    // 0.342, 32 -> 0.036 / 0.055 / 0.163 / 0.609 (MEASUREMENTS.md; the choice
+    // made by reading the code before these numbers was the gravity solver's,
+    // 8 up to 16 384 slots and 4 above)
+    if (p.solver == 7) g = nslots <= 2048 ? 32 : nslots <= 16384 ? 16 : 8;
     if (env_g == 1 || env_g == 2 || env_g == 4 || env_g == 8 || env_g == 16 || env_g == 32 || env_g == 64) g = env_g;
     switch (g) {
         case 64: go(std::integral_constant<int, 64>{}); break;
@@ -5429,13 +5529,16 @@ __global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t
 hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
                                uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
     if (nslots == 0) return hipSuccess;
-    if (p.solver != 3 && p.solver != 4 && p.solver != 5 && p.solver != 6) return hipErrorInvalidValue;
+    if (p.solver < 3 || p.solver > 7) return hipErrorInvalidValue;
     if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
                               (size_t)guided->stride * guided->buckets < guided->n))
         return hipErrorInvalidValue;
     const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
     auto run = [&](auto... t) {
-        if (p.solver == 6)
+        if (p.solver == 7)
+            hipLaunchKernelGGL((k_debug_sample<2, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
+                               nslots, attempt, out, t...);
+        else if (p.solver == 6)
             hipLaunchKernelGGL((k_debug_sample<3, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
                                nslots, attempt, out, t...);
         else if (p.solver == 5)
@@ -5609,7 +5712,7 @@ hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc,
                              uint32_t m, double Tm, BatchRecord* out, hipStream_t stream, const uint32_t* hmap,
                              const uint32_t* hcount) {
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(1), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 7 ? kSModels : solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
                        hcount);
     return hipGetLastError();
 }
@@ -5620,7 +5723,7 @@ hipError_t launch_select_geo_batches(int solver, const ScoreOut& sc, const uint8
     if (count == 0) return hipSuccess;
     if (stride < nh || stride == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(count), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 7 ? kSModels : solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
                        hcount, stride);
     return hipGetLastError();
 }

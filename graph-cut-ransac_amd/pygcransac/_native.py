@@ -23,6 +23,7 @@ GCR_ENODEV = -19
 SOLVER_SCALE3, SOLVER_SCALE3_ORIGINAL, SOLVER_SIFT22, SOLVER_HOMOGRAPHY4, SOLVER_FUNDAMENTAL7 = 0, 1, 2, 3, 4
 SOLVER_ESSENTIAL5 = 5    # problems of this kind come from gcr_problem_create_essential
 SOLVER_ESSENTIAL3_GRAVITY = 6   # ... from gcr_problem_create_gravity_essential
+SOLVER_HOMOGRAPHY2_SIFT = 7     # ... from gcr_problem_create_sift_homography
 FLAG_NO_LO = 1
 FLAG_GUIDED_STOP = 2     # guided sampling only: the adaptive stop on the inlier mass (csrc/guided_stop.h)
 
@@ -229,6 +230,12 @@ def _load():
     L.gcr_host_solve_g3.argtypes = [vp, C.c_size_t, vp, vp, vp, vp, u32p]
     L.gcr_host_fit_g.argtypes = [vp, C.c_size_t, vp, C.c_size_t, vp, vp, vp]
     L.gcr_host_generate_g.argtypes = [vp, C.c_size_t, vp, vp, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp, vp]
+    # homography from two SIFT correspondences (csrc/sifth.h): rows + N x 4 SIFT columns (q1, q2, alpha1, alpha2)
+    L.gcr_find_homography_sift.argtypes = [vp, vp, vp, C.c_size_t, vp, C.POINTER(Params), vp, vp, C.POINTER(Stats)]
+    L.gcr_problem_create_sift_homography.argtypes = [vp, vp, vp, C.c_size_t, C.POINTER(vp)]
+    L.gcr_host_check_sift.argtypes = [vp, C.c_size_t]
+    L.gcr_host_solve_s2.argtypes = [vp, vp, C.c_size_t, vp, vp, u32p]
+    L.gcr_host_generate_s.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp, vp]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

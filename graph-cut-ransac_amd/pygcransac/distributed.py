@@ -235,7 +235,7 @@ class Comm:
 
 def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None, rank: int = 0, world: int = 1,
                         dist=None, device: Optional[int] = None, coll_device=None, comm: Optional[Comm] = None,
-                        probabilities=None, K1=None, K2=None, G1=None, G2=None):
+                        probabilities=None, K1=None, K2=None, G1=None, G2=None, sift=None):
     """One estimator problem over `world` ranks.
 
     Every rank calls this with the same inputs; each verifies its block of
@@ -253,7 +253,9 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     Solver 5 (essential matrix) takes pixel rows and the calibration matrices
     `K1`, `K2` (3 x 3); its threshold is in pixels and H is E in normalised
     coordinates.  Solver 6 (essential matrix with known gravity) takes the
-    gravity-alignment rotations `G1`, `G2` (3 x 3) as well.
+    gravity-alignment rotations `G1`, `G2` (3 x 3) as well.  Solver 7
+    (homography from two SIFT correspondences) takes `sift`, the (N, 4) columns
+    q1, q2, alpha1, alpha2 of the rows in `f0`.
     Returns (H (3, 3) or None, masks tuple, stats dict, rect model record)."""
     import ctypes as C
 
@@ -280,6 +282,12 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
             N.check(N.lib.gcr_problem_create_gravity_essential(ctx, f0.ctypes.data, f0.shape[0], k1.ctypes.data,
                                                                k2.ctypes.data, g1.ctypes.data, g2.ctypes.data,
                                                                C.byref(h)))
+    elif solver == N.SOLVER_HOMOGRAPHY2_SIFT:
+        if sift is None:
+            raise ValueError("solver 7 (homography from two SIFT correspondences) needs sift")
+        sf = np.ascontiguousarray(sift, dtype=np.float64).reshape(f0.shape[0], 4)
+        N.check(N.lib.gcr_problem_create_sift_homography(ctx, f0.ctypes.data, sf.ctypes.data, f0.shape[0],
+                                                         C.byref(h)))
     else:
         N.check(N.lib.gcr_problem_create(ctx, solver, dp(f0), f0.shape[0], dp(f1) if f1 is not None else None,
                                          0 if f1 is None else f1.shape[0], C.byref(h)))

@@ -32,6 +32,7 @@ __all__ = [
     "findFundamentalMatrix",
     "findEssentialMatrix",
     "findGravityEssentialMatrix",
+    "findHomographySIFT",
 ]
 
 _TWO_PI = 2.0 * math.pi
@@ -444,7 +445,9 @@ def _as_probabilities(probabilities, n, m):
 
 def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                          spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
-                         batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False):
+                         batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False, min_weights=None):
+    """min_weights: the minimal sample size the probabilities are checked for
+    (default: min_rows)."""
     for name, v in (("h1", h1), ("w1", w1), ("h2", h2), ("w2", w2)):
         _as_double(v, name)
     sampler_id = _as_size_t(sampler, "sampler")
@@ -473,7 +476,7 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     mask = np.zeros(n, dtype=np.uint8)
     M = np.zeros(9, dtype=np.float64)
     st = N.Stats()
-    w = _as_probabilities(probabilities, n, min_rows) if sampler_id == 3 else None
+    w = _as_probabilities(probabilities, n, min_weights or min_rows) if sampler_id == 3 else None
     ctx = N.context(device)
     if sampler_id == 3:
         rc = guided_entry(ctx, f.ctypes.data, n, w.ctypes.data, C.byref(p), mask.ctypes.data, M.ctypes.data,
@@ -638,3 +641,51 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
     return _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                                 batch_slots, return_stats, 3, neighborhood_size, guided_stop)
+
+
+def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
+                       spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
+                       neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
+                       guided_stop=False):
+    """Homography from TWO SIFT correspondences with graph-cut LO -- an
+    EXTENSION like findHomography (what upstream pygcransac's findHomography
+    runs with its SIFT-based solver).  Upstream's solver is not part of this
+    project and parity with it is unpinned: csrc/sifth.h is the definition.
+
+    ``correspondences`` is (N, 8) float64: x1, y1, x2, y2 in pixels, the
+    feature sizes q1, q2 as lengths (cv2's ``kp.size`` or any fixed multiple of
+    it on both sides; finite, > 0) and the orientations alpha1, alpha2 in
+    RADIANS (finite); ``features.py`` hands out both.  A correspondence of two
+    oriented, scaled keypoints gives four constraints on H, so a sample is two
+    correspondences and yields up to three models: the stop needs about 113
+    iterations at 80 % outliers where findHomography needs about 2880.  A model
+    from two noisy features covers few inliers (an orientation error grows
+    with the distance from the sample), so the estimator rests on local
+    optimisation; scoring, the threshold, LO's fits (the 4-point estimator's
+    non-minimal fit), the neighbourhood grid and every other argument are
+    findHomography's.  ``probabilities`` (``sampler=3``) need at least 2 weights
+    > 0.
+
+    Returns ``(H, inliers)`` with H (3, 3) and H[2, 2] = 1, or ``(None, inliers)``.
+    """
+    f8 = _as_features(correspondences)
+    if f8.ndim != 2:
+        raise ValueError("Number of dimensions must be 2.")
+    n, cols = f8.shape
+    if n < 4 or cols != 8:
+        raise ValueError(f"Correspondences should be an array with 8 columns and at least 4 rows. "
+                         f"It has {cols} columns and {n} rows.")
+    sift = np.ascontiguousarray(f8[:, 4:8], dtype=np.float64)
+    # the engine's own check of the SIFT columns, before any GPU work
+    N.check(N.lib.gcr_host_check_sift(sift.ctypes.data, n))
+
+    def entry(ctx, f, n, p, mask, M, st):
+        return N.lib.gcr_find_homography_sift(ctx, f, sift.ctypes.data, n, None, p, mask, M, st)
+
+    def guided_entry(ctx, f, n, w, p, mask, M, st):
+        return N.lib.gcr_find_homography_sift(ctx, f, sift.ctypes.data, n, w, p, mask, M, st)
+
+    return _correspondence_call(entry, guided_entry, np.ascontiguousarray(f8[:, :4]), h1, w1, h2, w2, probabilities,
+                                threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
+                                seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
+                                min_weights=2)

@@ -245,3 +245,49 @@ def problem_g(n: int = 10_000, outlier_ratio: float = 0.8, seed: int = DEFAULT_S
     truth = np.concatenate([np.ones(n_in, bool), np.zeros(n_out, bool)])
     perm = rng.permutation(n)
     return np.ascontiguousarray(corr[perm]), truth[perm], K, G1, G2, E
+
+
+def affine_of_h(H: np.ndarray, x1, y1):
+    """The local affine map of the homography H at the points (x1, y1): the
+    Jacobian of x -> H x, (n, 2, 2)."""
+    x1 = np.asarray(x1, dtype=float)
+    y1 = np.asarray(y1, dtype=float)
+    s = H[2, 0] * x1 + H[2, 1] * y1 + H[2, 2]
+    x2 = (H[0, 0] * x1 + H[0, 1] * y1 + H[0, 2]) / s
+    y2 = (H[1, 0] * x1 + H[1, 1] * y1 + H[1, 2]) / s
+    A = np.empty(x1.shape + (2, 2))
+    A[..., 0, 0] = (H[0, 0] - x2 * H[2, 0]) / s
+    A[..., 0, 1] = (H[0, 1] - x2 * H[2, 1]) / s
+    A[..., 1, 0] = (H[1, 0] - y2 * H[2, 0]) / s
+    A[..., 1, 1] = (H[1, 1] - y2 * H[2, 1]) / s
+    return A
+
+
+def problem_hs(n: int = 5_000, outlier_ratio: float = 0.5, seed: int = DEFAULT_SEED, noise: float = 0.5,
+               scale_noise: float = 0.05, angle_noise: float = math.radians(2.0), H: np.ndarray = H_GT):
+    """Homography problem with SIFT columns: problem_h's rows (the same rows
+    bit for bit) plus q1, q2, alpha1, alpha2.  Inliers: q1 log-uniform in
+    [2, 30], alpha1 uniform in [-pi, pi), alpha2 and q2 from the true local
+    affine map A of H at (x1, y1) -- the direction of A d1 and q1 sqrt(det A)
+    -- with Gaussian noise `angle_noise` (radians) on alpha2 and lognormal
+    noise `scale_noise` on q2.  Outliers: all four columns random.  Returns
+    correspondences (n, 8), inlier truth mask, ground-truth H and the inlier
+    threshold (px)."""
+    corr, truth, Hgt, thr = problem_h(n, outlier_ratio, seed, noise, H)
+    rng = np.random.default_rng([seed, 0x73696674])
+    q1 = np.exp(rng.uniform(math.log(2.0), math.log(30.0), n))
+    a1 = rng.uniform(-math.pi, math.pi, n)
+    q2 = np.exp(rng.uniform(math.log(2.0), math.log(30.0), n))
+    a2 = rng.uniform(-math.pi, math.pi, n)
+    en = rng.normal(0.0, 1.0, n)
+    sn = rng.normal(0.0, 1.0, n)
+    A = affine_of_h(H, corr[:, 0], corr[:, 1])
+    dx, dy = np.cos(a1), np.sin(a1)
+    tx = A[:, 0, 0] * dx + A[:, 0, 1] * dy
+    ty = A[:, 1, 0] * dx + A[:, 1, 1] * dy
+    det = A[:, 0, 0] * A[:, 1, 1] - A[:, 0, 1] * A[:, 1, 0]
+    a2_in = np.arctan2(ty, tx) + angle_noise * en
+    q2_in = q1 * np.sqrt(np.abs(det)) * np.exp(scale_noise * sn)
+    a2 = np.where(truth, a2_in, a2)
+    q2 = np.where(truth, q2_in, q2)
+    return np.ascontiguousarray(np.column_stack([corr, q1, q2, a1, a2])), truth, Hgt, thr

@@ -42,8 +42,9 @@ extern "C" {
  * gcr_params.flags (a call that leaves it clear runs as before), its host
  * and debug entries are new functions.  The essential-matrix estimator
  * (GCR_SOLVER_ESSENTIAL5) likewise: new functions and a new solver kind only;
- * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY), and the
- * host hook gcr_host_guided_index. */
+ * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY), the
+ * host hook gcr_host_guided_index, and the homography from two SIFT
+ * correspondences (GCR_SOLVER_HOMOGRAPHY2_SIFT). */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -65,6 +66,9 @@ extern "C" {
 #define GCR_SOLVER_ESSENTIAL3_GRAVITY 6 /* 3-point essential matrix with the gravity direction
                                         of both cameras known; problems of this kind come
                                         from gcr_problem_create_gravity_essential */
+#define GCR_SOLVER_HOMOGRAPHY2_SIFT 7 /* homography from two SIFT correspondences (point, feature
+                                        size and orientation); problems of this kind come from
+                                        gcr_problem_create_sift_homography */
 
 typedef struct gcr_ctx gcr_ctx;
 typedef struct gcr_problem gcr_problem;
@@ -242,6 +246,27 @@ int gcr_find_gravity_essential_matrix(gcr_ctx* ctx, const double* correspondence
                                       const double* probabilities, const gcr_params* params, uint8_t* mask_out,
                                       double* E_out, gcr_stats* stats_out);
 
+/* Homography from two SIFT correspondences (an EXTENSION -- what upstream
+ * pygcransac's findHomography binds as its SIFT-based solver; parity with
+ * upstream is unpinned, csrc/sifth.h is the definition).  correspondences:
+ * N x 4 rows x1, y1, x2, y2 in pixels; sift: N x 4 rows q1, q2, alpha1,
+ * alpha2 -- the feature sizes as lengths (any fixed multiple of them on both
+ * sides) and the orientations in radians.  A q that is not finite and > 0 or
+ * an alpha that is not finite is GCR_EINVAL with a message naming the column
+ * (q1, q2, alpha1, alpha2), before any GPU work; n < 4 is GCR_EINVAL.  A
+ * sample is two correspondences and yields up to three models; scoring, the
+ * inlier threshold, local optimisation (its fits are the 4-point estimator's
+ * non-minimal fit, on samples of up to 14), the neighbourhood grid and H_out
+ * (H[8] = 1) are gcr_find_homography's.  probabilities: NULL (uniform) or n
+ * weights with at least 2 of them > 0 (guided, as
+ * gcr_find_homography_guided).  A minimal model covers few inliers (an
+ * orientation error is multiplied by the distance from the sample), so the
+ * estimator rests on local optimisation: GCR_FLAG_NO_LO makes little sense
+ * here. */
+int gcr_find_homography_sift(gcr_ctx* ctx, const double* correspondences, const double* sift, size_t n,
+                             const double* probabilities, const gcr_params* params, uint8_t* mask_out, double* H_out,
+                             gcr_stats* stats_out);
+
 /* ---- batches of independent problems (SURVEY.md §8(b) gcr_rect_batch,
  * BASELINE configs[4]) ----------------------------------------------------- */
 typedef struct gcr_batch_item {
@@ -288,6 +313,15 @@ int gcr_problem_create_essential(gcr_ctx* ctx, const double* correspondences, si
  * GCR_EINVAL; everything the essential problem is accepted by accepts this one. */
 int gcr_problem_create_gravity_essential(gcr_ctx* ctx, const double* correspondences, size_t n, const double* K1,
                                          const double* K2, const double* G1, const double* G2, gcr_problem** out);
+/* A homography problem plus the SIFT columns (GCR_SOLVER_HOMOGRAPHY2_SIFT),
+ * checked as gcr_find_homography_sift checks them.  n >= 2 is accepted (the
+ * generator and sampler hooks work on it); the run entries -- gcr_problem_run,
+ * _run_sharded, _run_comm, _verify_batch(es) -- need n >= 4 and are GCR_EINVAL
+ * below that.  gcr_problem_create(7, ...) and items of gcr_solve_batch of kind
+ * 7 are GCR_EINVAL; everything the homography problem is accepted by accepts
+ * this one (gcr_problem_set_probabilities: at least 2 weights > 0). */
+int gcr_problem_create_sift_homography(gcr_ctx* ctx, const double* correspondences, const double* sift, size_t n,
+                                       gcr_problem** out);
 void gcr_problem_destroy(gcr_problem* prob);
 /* Guided sampling for a resident homography / fundamental-matrix problem (see
  * gcr_find_homography_guided): n must be the problem's N.  Everything that
@@ -402,11 +436,11 @@ int gcr_host_fit_nonminimal(int solver, const double* f0, size_t n0, const doubl
  * doubles per slot): inc[3s] as above, inc[3s+k] = 0 if the sample's k-th
  * model exists, 255 if not; essential -- the same with 10 hypotheses per slot
  * (inc_out 10 bytes, H_out 90 doubles per slot), gravity essential with 4
- * (4 bytes, 36 doubles).  score: n0 / v0 / tot per model (MSAC threshold
+ * (4 bytes, 36 doubles), SIFT homography with 3 (3 bytes, 27 doubles).  score: n0 / v0 / tot per model (MSAC threshold
  * 2.25 thr); mask: rules as gcr_debug_mask */
 int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc_out,
                          double* H_out);
-/* the generators' sampling function alone: the 4 / 7 / 5 / 3 (solvers 3 .. 6)
+/* the generators' sampling function alone: the 4 / 7 / 5 / 3 / 2 (solvers 3 .. 7)
  * indices of attempt `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out:
  * as many per slot,
  * all-ones where the draw budget ran out), with the problem's sampler --
@@ -478,6 +512,23 @@ int gcr_host_fit_g(const double* correspondences_normalised, size_t n, const uin
 int gcr_host_generate_g(const double* correspondences_normalised, size_t n, const double* G1, const double* G2,
                         const double* probabilities, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
                         uint8_t* inc_out, double* models_out);
+/* host-only, homography from two SIFT correspondences (csrc/sifth.h).
+ * correspondences: N x 4 pixel rows; sift: N x 4 rows q1, q2, alpha1, alpha2.
+ * check_sift: gcr_find_homography_sift's check of the columns alone.
+ * solve_s2: the 2-point solver on the two listed rows (their SIFT entries are
+ * checked; gcr_host_solve_minimal(7, ...) cannot carry the columns and is
+ * GCR_EINVAL): *count_out = 0 .. 3 models in ascending root order, 9 doubles
+ * each, models_out needs room for 27.
+ * generate_s: the host twin of the generator, over `threads` host threads:
+ * gcr_debug_generate_h's inc_out (3 bytes per slot) and models (27 doubles per
+ * slot) bit for bit; probabilities NULL = uniform draws, else guided (n
+ * weights). */
+int gcr_host_check_sift(const double* sift, size_t n);
+int gcr_host_solve_s2(const double* correspondences, const double* sift, size_t n, const uint32_t* idx,
+                      double* models_out, uint32_t* count_out);
+int gcr_host_generate_s(const double* correspondences, const double* sift, size_t n, const double* probabilities,
+                        uint64_t seed, uint64_t slot0, uint32_t nslots, int threads, uint8_t* inc_out,
+                        double* models_out);
 /* host-only: RectifyingHomography::getHomography (model.h:211-226), row-major */
 void gcr_host_homography(const gcr_rect_model* model, double* H_out);
 /* host-only: squared residuals of one rectification model over n features of
