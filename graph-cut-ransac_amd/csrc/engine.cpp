@@ -5573,6 +5573,58 @@ int gcr_debug_score(gcr_problem* prob, const gcr_params* params, const gcr_rect_
     });
 }
 
+int gcr_debug_verify_slots(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
+                           uint8_t* inc_out, uint32_t* n0, uint32_t* n1, double* v0, double* v1, double* tot) {
+    if (!prob || !inc_out || !n0 || !n1 || !v0 || !v1 || !tot) return set_err(GCR_EINVAL, "null argument");
+    if (prob->solver > 2) return set_err(GCR_EINVAL, "gcr_debug_verify_slots: rectification solvers only");
+    if (int e = check_params(params, prob->solver)) return e;
+    if (nslots == 0) return set_err(GCR_EINVAL, "nslots must be > 0");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        hipStream_t s = prob->ctx->stream;
+        Workspace* w = prob->w;
+        double T[2];
+        const double thr[2] = {params->scale_residual_thresh, params->orientation_residual_thresh};
+        for (int c = 0; c < 2; ++c) T[c] = (2.25 * thr[c]) * thr[c];
+        const uint32_t m32[2] = {(uint32_t)minimal_size(prob->solver), 2u};
+        const size_t wg_cap = (nslots + 3) / 4;
+        w->inc.ensure(nslots);
+        w->models.ensure(nslots);
+        w->sb.ensure(nslots);
+        w->wg.ensure(wg_cap);
+        // what a one-batch gcr_problem_verify_batches call launches, without
+        // its selection: no chain, one group
+        HIPC(launch_verify_fused(prob->dp, T, params->seed, slot0, nslots, m32, w->inc.p, w->models.p, w->sb.dev(),
+                                 w->wg.p, wg_cap, nullptr, nullptr, nullptr, s, GenChain{}));
+        std::vector<RectModel> hm(nslots);
+        HIPC(hipMemcpyAsync(inc_out, w->inc.p, nslots, hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(hm.data(), w->models.p, (size_t)nslots * sizeof(RectModel), hipMemcpyDeviceToHost, s));
+        w->sb.d2h(nslots, s);
+        HIPC(hipStreamSynchronize(s));
+        std::memcpy(n0, w->sb.hn0.p, nslots * sizeof(uint32_t));
+        std::memcpy(n1, w->sb.hn1.p, nslots * sizeof(uint32_t));
+        std::memcpy(v0, w->sb.hv0.p, nslots * sizeof(double));
+        std::memcpy(v1, w->sb.hv1.p, nslots * sizeof(double));
+        std::memcpy(tot, w->sb.htot.p, nslots * sizeof(double));
+        // flagged decisions as in gcr_debug_score of the slot's stored model
+        if (exact_on()) {
+            ExactCount ec;
+            for (uint32_t i = 0; i < nslots; ++i)
+                if (inc_out[i] <= 101 && (w->sb.hfl.p[i] != 0 || model_unsafe(prob, hm[i], T[0]))) {
+                    uint32_t n[2];
+                    double v[2];
+                    exact_accumulate(prob, hm[i], hm[i], T, n, v, tot[i], nullptr, ec);
+                    n0[i] = n[0];
+                    n1[i] = prob->K == 2 ? n[1] : 0;
+                    v0[i] = v[0];
+                    v1[i] = prob->K == 2 ? v[1] : 0.0;
+                }
+        }
+        return GCR_OK;
+    });
+}
+
 size_t gcr_debug_exchange_log(uint64_t* out, size_t cap) {
     const size_t n = t_xlog.size();
     if (out) std::memcpy(out, t_xlog.data(), std::min(n, cap) * sizeof(uint64_t));

@@ -400,6 +400,13 @@ int gcr_debug_generate(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_
 /* raw MSAC accumulators for explicit models: counts, per-class sums, total */
 int gcr_debug_score(gcr_problem* prob, const gcr_params* params, const gcr_rect_model* models, uint32_t nmodels,
                     uint32_t* n0, uint32_t* n1, double* v0, double* v1, double* tot);
+/* every slot of one fused generate + score launch (rectification solvers): what
+ * a one-batch gcr_problem_verify_batches call launches (unchained, one group),
+ * without its selection.  inc_out[i] as gcr_debug_generate's, the raw MSAC
+ * accumulators as gcr_debug_score's (zeros for a slot without a model); the
+ * sampler seed is params->seed */
+int gcr_debug_verify_slots(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
+                           uint8_t* inc_out, uint32_t* n0, uint32_t* n1, double* v0, double* v1, double* tot);
 /* The run loop's score comparison `score(a) < score(b)` (GCRANSAC.h:440) as
  * gcr_problem_run takes it: both models scored by the GPU small scorer (value
  * scores), compared directly when they are further apart than their proven

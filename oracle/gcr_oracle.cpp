@@ -2828,6 +2828,25 @@ int oracle_score(int kind, const double* f0, size_t n0, const double* f1, size_t
     return 0;
 }
 
+// oracle_slot + oracle_score of `nslots` consecutive slots under `nthr`
+// threshold pairs (thr[2 t], thr[2 t + 1]), in one call: inc[s], models7[7 s],
+// and for threshold pair t counts[2 (t nslots + s)], values[2 (t nslots + s)],
+// value[t nslots + s] -- left untouched for a slot without a model
+int oracle_slots_scored(int kind, const double* f0, size_t n0, const double* f1, size_t n1, uint64_t seed,
+                        uint64_t slot0, size_t nslots, int math_mode, const double* thr, size_t nthr, int* inc,
+                        double* models7, uint64_t* counts, double* values, double* value) {
+    for (size_t s = 0; s < nslots; ++s) {
+        inc[s] = oracle_slot(kind, f0, n0, f1, n1, seed, slot0 + s, math_mode, models7 + 7 * s);
+        if (inc[s] > 101) continue;
+        for (size_t t = 0; t < nthr; ++t) {
+            const size_t o = t * nslots + s;
+            oracle_score(kind, f0, n0, f1, n1, models7 + 7 * s, thr[2 * t], thr[2 * t + 1], math_mode, counts + 2 * o,
+                         values + 2 * o, value + o, nullptr, nullptr);
+        }
+    }
+    return 0;
+}
+
 // per-feature squared residuals of one model
 // The score comparison `score(a) < score(b)` of the run loop (GCRANSAC.h:440)
 // in math_mode: GLIBC compares the glibc scores, TWIN the value scores with

@@ -61,6 +61,8 @@ def lib():
         L.oracle_score.argtypes = [C.c_int, dp, C.c_size_t, dp, C.c_size_t, dp, C.c_double, C.c_double, C.c_int,
                                    u64p, dp, dp, u8p, u8p]
         L.oracle_residuals.argtypes = [C.c_int, C.c_int, dp, C.c_size_t, dp, C.c_int, dp]
+        L.oracle_slots_scored.argtypes = [C.c_int, dp, C.c_size_t, dp, C.c_size_t, C.c_uint64, C.c_uint64, C.c_size_t,
+                                          C.c_int, dp, C.c_size_t, C.POINTER(C.c_int), dp, u64p, dp, dp]
         L.oracle_sample.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
                                     C.c_uint32, u64p]
         L.oracle_philox.argtypes = [C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32)]
@@ -221,6 +223,27 @@ def score(kind, f0, f1, model, thr0, thr1=0.0, math_mode=MATH_TWIN, want_masks=F
     if want_masks:
         out["masks"] = (m0.astype(bool), None if m1 is None else m1.astype(bool))
     return out
+
+
+def slots_scored(kind, f0, f1, seed, slot0, nslots, thresholds, math_mode=MATH_TWIN):
+    """slot() and score() of nslots consecutive slots under every (thr0, thr1)
+    of `thresholds`, in one call (the GIL is released for all of it): inc
+    (n,), models (n, 7), counts (t, n, 2), values (t, n, 2), value (t, n);
+    zeros for a slot without a model."""
+    f0 = _f64(f0)
+    f1 = _f64(f1) if f1 is not None else None
+    thr = _f64(thresholds).reshape(-1, 2)
+    t = thr.shape[0]
+    inc = np.zeros(nslots, dtype=np.int32)
+    models = np.zeros((nslots, 7))
+    counts = np.zeros((t, nslots, 2), dtype=np.uint64)
+    values = np.zeros((t, nslots, 2))
+    value = np.zeros((t, nslots))
+    lib().oracle_slots_scored(kind, _dp(f0), f0.shape[0], _dp(f1) if f1 is not None else None,
+                              0 if f1 is None else f1.shape[0], seed, slot0, nslots, math_mode, _dp(thr), t,
+                              inc.ctypes.data_as(C.POINTER(C.c_int)), _dp(models),
+                              counts.ctypes.data_as(C.POINTER(C.c_uint64)), _dp(values), _dp(value))
+    return inc, models, counts, values, value
 
 
 def residuals(kind, cls, f, model, math_mode=MATH_TWIN):
