@@ -567,21 +567,16 @@ void comm_sync(hipEvent_t ev, ncclComm_t comm, const char* what) {
 }
 }  // namespace
 
+// solver.h's table under the names the engine uses
 // the calibrated estimators: K-normalised rows, pixel grid, pixel threshold
-static inline bool is_ess(int solver) {
-    return solver == GCR_SOLVER_ESSENTIAL5 || solver == GCR_SOLVER_ESSENTIAL3_GRAVITY;
-}
-
-// minimal sample size of a solver kind (6, gravity: 3, as 0 and 1; 7, SIFT
-// homography: 2)
-static inline size_t minimal_size(int solver) {
-    return solver == 2 || solver == GCR_SOLVER_HOMOGRAPHY2_SIFT ? 2
-           : solver == 3 ? 4 : solver == 4 ? 7 : solver == 5 ? 5 : 3;
-}
+static inline bool is_ess(int solver) { return solver_row(solver).calibrated; }
+// the correspondence estimators (GeoModel, N x 4 rows)
+static inline bool is_corr(int solver) { return solver_row(solver).corr; }
+static inline size_t minimal_size(int solver) { return (size_t)solver_row(solver).m; }
 
 struct gcr_problem {
     gcr_ctx* ctx = nullptr;
-    int solver = 0;
+    int solver = 0;                     // the estimator; dp.kind is its residual kind (solver.h)
     int K = 1;
     HostClass hc[2];
     DevProblem dp{};
@@ -605,43 +600,26 @@ struct gcr_problem {
         const char* e = getenv("GCR_GUIDED_FLAT");
         return (e && e[0] == '1') ? &gt_flat : &gt;
     }
-    // Essential matrix (solver 5): hc[0] and the device SoA hold the
-    // K-normalised correspondences, and dp.solver is 4, so scoring, masks,
-    // residuals and the inlier mass are the fundamental matrix's (squared
-    // Sampson distance).  Host only: the pixel columns (the neighbourhood
+    // Calibrated solvers: hc[0] and the device SoA hold the K-normalised
+    // correspondences.  Host only: the pixel columns (the neighbourhood
     // grid is built over them) and the divisor that takes a pixel threshold
     // to normalised coordinates.
     std::vector<double> pix[4];
     double thr_div = 1.0;
-    // Essential matrix with known gravity (solver 6): an essential problem plus
-    // the two gravity-alignment rotations, which the generator launches and
-    // the host fit get (grav.h)
+    // Essential matrix with known gravity: the two gravity-alignment
+    // rotations, which the generator launches and the host fit get (grav.h)
     GravRot rot{};
-    const GravRot* grav() const { return solver == GCR_SOLVER_ESSENTIAL3_GRAVITY ? &rot : nullptr; }
-    // Homography from two SIFT correspondences (solver 7): a homography
-    // problem (dp.solver is 3: scoring, masks, residuals, the inlier mass and
-    // the non-minimal fit are the homography's) plus the stored SIFT columns
+    const GravRot* grav() const { return solver_row(solver).needs_gravity ? &rot : nullptr; }
+    // Homography from two SIFT correspondences: the stored SIFT columns
     // (sifth.h), which live behind the classes in the workspace's feat and go
     // to the generator launches alone
     SiftCols scols{};
-    const SiftCols* sift() const { return solver == GCR_SOLVER_HOMOGRAPHY2_SIFT ? &scols : nullptr; }
-    // what the generator launches get: the problem's own solver kind
-    DevProblem gen_dp() const {
-        DevProblem d = dp;
-        d.solver = solver;
-        return d;
-    }
+    const SiftCols* sift() const { return solver_row(solver).needs_sift ? &scols : nullptr; }
     // the residual threshold of params in the units of hc[0]
     double thr0(const gcr_params& prm) const {
         return is_ess(solver) ? prm.scale_residual_thresh / thr_div : prm.scale_residual_thresh;
     }
 };
-
-// the correspondence estimators (GeoModel, N x 4 rows)
-static inline bool is_corr(int solver) {
-    return solver == GCR_SOLVER_HOMOGRAPHY4 || solver == GCR_SOLVER_FUNDAMENTAL7 || is_ess(solver) ||
-           solver == GCR_SOLVER_HOMOGRAPHY2_SIFT;
-}
 
 namespace {
 
@@ -658,8 +636,9 @@ double host_r2(const gcr_problem* P, int cls, size_t i, const RectModel& m) {
     const HostClass& h = P->hc[cls];
     if (cls == 0) {
         const double ac = alpha_cube(m);
-        return P->solver == 1 ? scale_sq_residual<true, false, M>(h.x[i], h.y[i], h.a[i], m, ac)
-                              : scale_sq_residual<false, false, M>(h.x[i], h.y[i], h.a[i], m, ac);
+        return P->solver == GCR_SOLVER_SCALE3_ORIGINAL
+                   ? scale_sq_residual<true, false, M>(h.x[i], h.y[i], h.a[i], m, ac)
+                   : scale_sq_residual<false, false, M>(h.x[i], h.y[i], h.a[i], m, ac);
     }
     return orient_sq_residual<false, M>(h.x[i], h.y[i], h.c0[i], h.c1[i], m, orient_const(m));
 }
@@ -669,8 +648,9 @@ double host_r2(const gcr_problem* P, int cls, size_t i, const RectModel& m) {
 double host_value(const gcr_problem* P, int cls, size_t i, const RectModel& m, const ValueConst& vc) {
     const HostClass& h = P->hc[cls];
     if (cls == 0)
-        return P->solver == 1 ? scale_sq_value<true, false>(h.x[i], h.y[i], h.a[i], m, vc.ac, vc.cut)
-                              : scale_sq_value<false, false>(h.x[i], h.y[i], h.a[i], m, vc.ac, vc.cut);
+        return P->solver == GCR_SOLVER_SCALE3_ORIGINAL
+                   ? scale_sq_value<true, false>(h.x[i], h.y[i], h.a[i], m, vc.ac, vc.cut)
+                   : scale_sq_value<false, false>(h.x[i], h.y[i], h.a[i], m, vc.ac, vc.cut);
     return orient_sq_value<false>(h.x[i], h.y[i], h.c0[i], h.c1[i], m, vc.c, vc.s, vc.cphi, vc.cphi2);
 }
 
@@ -691,7 +671,7 @@ bool exact_on() {
 }
 
 bool model_unsafe(const gcr_problem* P, const RectModel& m, double T0) {
-    return P->solver <= 2 && scale_unsafe(P->solver, m.alpha, T0, P->scales_ok);
+    return solver_row(P->solver).rect && scale_unsafe(P->solver, m.alpha, T0, P->scales_ok);
 }
 
 // The MSAC accumulators of one model with every decision in the reference's
@@ -980,7 +960,7 @@ void exact_accumulate(const gcr_problem* P, const RectModel& mv, const RectModel
         double* const vp = val.data();
         uint8_t* const dp = dec.data();
         std::atomic<uint64_t> flips{0};
-        const ValueConst vc = value_const(mv, P->solver == 1, c == 1);
+        const ValueConst vc = value_const(mv, P->solver == GCR_SOLVER_SCALE3_ORIGINAL, c == 1);
         auto body = [&](size_t lo, size_t hi) {
             uint64_t f = 0;
             for (size_t i = lo; i < hi; ++i) {
@@ -1158,9 +1138,9 @@ struct FillOut {
 };
 FillOut fill_host_classes(int solver, const double* f0, size_t n0, const double* f1, size_t n1, HostClass* hc,
                           double* hst, const size_t np[2], const size_t off[2]) {
-    const bool corr = solver == 3 || solver == 4;
-    const int K = solver == 2 ? 2 : 1;
-    const double kScalePower = (solver == 1) ? (-1.0 / 3.0) : (1.0 / 3.0);
+    const bool corr = solver_row(solver).corr;
+    const int K = solver_row(solver).classes;
+    const double kScalePower = (solver == GCR_SOLVER_SCALE3_ORIGINAL) ? (-1.0 / 3.0) : (1.0 / 3.0);
     const double* src[2] = {f0, f1};
     const size_t ns[2] = {n0, K == 2 ? n1 : 0};
     FillOut res{};
@@ -1247,7 +1227,7 @@ FillOut fill_host_classes(int solver, const double* f0, size_t n0, const double*
             res.amax[c][q] = c < K ? (bad ? HUGE_VAL : mx) : 0.0;
         }
         if (c >= K) continue;
-        if (c == 0 && solver <= 2)
+        if (c == 0 && solver_row(solver).rect)
             for (int p = 0; p < np_; ++p) res.scales_ok = res.scales_ok && (pr[p].c != 0 || pr[p].range);
         for (int q = 0; q < 5; ++q)
             for (size_t i = ns[c]; i < np[c]; ++i) d[c][q][i] = 0.0;      // pads
@@ -1257,7 +1237,7 @@ FillOut fill_host_classes(int solver, const double* f0, size_t n0, const double*
 
 // the host classes alone (debug and host-only entry points)
 void fill_host_classes(int solver, const double* f0, size_t n0, const double* f1, size_t n1, HostClass* hc) {
-    const size_t n1k = solver == 2 ? n1 : 0;
+    const size_t n1k = solver_row(solver).classes == 2 ? n1 : 0;
     const size_t np[2] = {(n0 + 1) & ~size_t(1), (n1k + 1) & ~size_t(1)};
     const size_t off[2] = {0, 5 * np[0]};
     std::vector<double> stage(5 * (np[0] + np[1]));
@@ -1356,8 +1336,8 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
                  const double* K2 = nullptr, const double* G1 = nullptr, const double* G2 = nullptr,
                  const double* sift = nullptr) {
     const bool ess = is_ess(solver);
-    const bool grv = solver == GCR_SOLVER_ESSENTIAL3_GRAVITY;
-    const bool sfh = solver == GCR_SOLVER_HOMOGRAPHY2_SIFT;
+    const bool grv = solver_row(solver).needs_gravity;
+    const bool sfh = solver_row(solver).needs_sift;
     if (sfh && sift == nullptr)
         return set_err(GCR_EINVAL, "solver 7 (homography from two SIFT correspondences) needs the SIFT columns: use "
                                    "gcr_problem_create_sift_homography or gcr_find_homography_sift");
@@ -1369,8 +1349,8 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
         return set_err(GCR_EINVAL, "solver 5 (essential matrix) needs the calibration matrices: use "
                                    "gcr_problem_create_essential or gcr_find_essential_matrix");
     if (!ctx || !out) return set_err(GCR_EINVAL, "null context or output pointer");
-    if (solver < 0 || solver > 7) return set_err(GCR_EINVAL, "unknown solver %d", solver);
-    const int K = solver == 2 ? 2 : 1;
+    if (!solver_known(solver)) return set_err(GCR_EINVAL, "unknown solver %d", solver);
+    const int K = solver_row(solver).classes;
     const size_t m0 = minimal_size(solver);
     if (!f0 || (K == 2 && !f1)) return set_err(GCR_EINVAL, "null feature pointer");
     if (ess) {
@@ -1416,9 +1396,8 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
             P->rot.g1[k] = G1[k];
             P->rot.g2[k] = G2[k];
         }
-    // the host / device classes and the kernels' KIND: the fundamental matrix's
-    // (the SIFT homography's: the homography's)
-    const int dsolver = ess ? GCR_SOLVER_FUNDAMENTAL7 : sfh ? GCR_SOLVER_HOMOGRAPHY4 : solver;
+    // what the host / device classes are filled for and the kernels' KIND
+    const int kind = solver_row(solver).kind;
     const size_t ns[2] = {n0, K == 2 ? n1 : 0};
     std::vector<std::pair<const char*, Clock::time_point>> st;      // GCR_LO_TRACE: "gcr SETUP:"
     if (g_lo_trace) st.emplace_back("start", Clock::now());
@@ -1458,8 +1437,8 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
     if (g_lo_trace) st.emplace_back("ws", Clock::now());
     double* hst = P->w->feat_stage.p;
     const size_t off[2] = {0, 5 * np[0]};
-    const FillOut fo = fill_host_classes(dsolver, f0, n0, f1, n1, P->hc, hst, np, off);
-    if (solver <= 2) P->scales_ok = fo.scales_ok;
+    const FillOut fo = fill_host_classes(kind, f0, n0, f1, n1, P->hc, hst, np, off);
+    if (solver_row(solver).rect) P->scales_ok = fo.scales_ok;
     if (sfh) {
         double* col = hst + soff;
         // (the trig of 10 000 rows is 0.3 ms on one thread: in parts on the host pool, as the classes' fill)
@@ -1478,7 +1457,7 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
         P->scols = SiftCols{d, d + np[0], d + 2 * np[0], d + 3 * np[0], d + 4 * np[0]};
     }
     if (g_lo_trace) st.emplace_back("fill", Clock::now());
-    P->dp.solver = dsolver;
+    P->dp.kind = kind;
     for (int c = 0; c < 2; ++c) {
         DevClass& d = P->dp.cls[c];
         d.n = (uint32_t)ns[c];
@@ -1528,10 +1507,10 @@ int make_problem(gcr_ctx* ctx, int solver, const double* f0, size_t n0, const do
 
 // ---------------------------------------------------------------- runner ----
 // Estimator traits of the host engine: model type, kernels and host fits of
-// the rectification solvers (0-2) and the homography (3).
+// the rectification solvers (0-2) and the homography (3).  kPer: solver.h's `per`.
 struct RectTraits {
     using Model = RectModel;
-    static constexpr size_t kPer = 1;
+    static constexpr size_t kPer = kSolverTable[GCR_SOLVER_SCALE3].per;
     static constexpr bool kFusedVerify = true;    // verify = one fused generate + score launch
     static Model def() { return default_model(); }
     static DevBuf<Model>& dmodels(Workspace* w) { return w->models; }
@@ -1541,7 +1520,7 @@ struct RectTraits {
     static DevBuf<Model>& lomodels(Workspace* w) { return w->lo_models; }
     static PinBuf<Model>& hlomodels(Workspace* w) { return w->h_lorect; }
     static bool identity(const Model& m) { return identity_norm(m); }
-    static bool valid(int solver, const Model& m) { return solver == 2 ? valid_model_sift22(m) : true; }
+    static bool valid(int solver, const Model& m) { return solver == GCR_SOLVER_SIFT22 ? valid_model_sift22(m) : true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
         return launch_generate(P->dp, seed, s0, n, inc, m, s);
@@ -1770,7 +1749,7 @@ struct RectTraits {
 
 struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     using Model = GeoModel;
-    static constexpr size_t kPer = 1;
+    static constexpr size_t kPer = kSolverTable[GCR_SOLVER_HOMOGRAPHY4].per;
     static constexpr bool kFusedVerify = false;   // verify = generation + scoring launches
     static Model def() { return default_geo(); }
     static DevBuf<Model>& dmodels(Workspace* w) { return w->gmodels; }
@@ -1783,7 +1762,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static bool valid(int, const Model&) { return true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
-        return launch_generate_geo(P->gen_dp(), seed, s0, n, inc, m, s, P->guided(), P->grav(), P->sift());
+        return launch_generate_geo(P->solver, P->dp, seed, s0, n, inc, m, s, P->guided(), P->grav(), P->sift());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1842,7 +1821,8 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     }
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
-        hipError_t e = launch_generate_geo(P->gen_dp(), seed, s0, n, b.inc, b.models, s, P->guided(), P->grav(), P->sift());
+        hipError_t e = launch_generate_geo(P->solver, P->dp, seed, s0, n, b.inc, b.models, s, P->guided(), P->grav(),
+                                           P->sift());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -1922,15 +1902,14 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
         return launch_score_geo(P->dp, T[0], m, inc, std::max<uint32_t>(live, 1u), out, s, P->w->hmap.p,
                                 P->w->hcount.p);
     }
-    static size_t per(gcr_problem* P) {
-        return P->solver == 4 ? kFModels : P->solver == 5 ? kEModels : P->solver == 6 ? kGModels
-               : P->solver == 7 ? kSModels : 1;
-    }
+    static size_t per(gcr_problem* P) { return (size_t)solver_row(P->solver).per; }
     static bool fit(gcr_problem* P, const std::vector<uint32_t>* lists, Model& out, bool) {
-        if (P->solver == 6) return fit_g3_nonminimal(P->hc[0], lists[0], P->rot, out);
-        if (P->solver == 5) return fit_e5_nonminimal(P->hc[0], lists[0], out);
-        if (P->solver == 4) return fit_f8_nonminimal(P->hc[0], lists[0], out);
-        return fit_h4_nonminimal(P->hc[0], lists[0], out);
+        switch (P->solver) {
+            case GCR_SOLVER_ESSENTIAL3_GRAVITY: return fit_g3_nonminimal(P->hc[0], lists[0], P->rot, out);
+            case GCR_SOLVER_ESSENTIAL5: return fit_e5_nonminimal(P->hc[0], lists[0], out);
+            case GCR_SOLVER_FUNDAMENTAL7: return fit_f8_nonminimal(P->hc[0], lists[0], out);
+            default: return fit_h4_nonminimal(P->hc[0], lists[0], out);      // both homography solvers
+        }
     }
     static void output(const Model& m, double* H, gcr_rect_model*) {
         for (int k = 0; k < 9; ++k) H[k] = m.h[k];
@@ -1938,7 +1917,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
 };
 
 struct FundTraits : GeoTraits {     // up to kFModels models per sample
-    static constexpr size_t kPer = kFModels;
+    static constexpr size_t kPer = kSolverTable[GCR_SOLVER_FUNDAMENTAL7].per;
     // summary replay: the live hypotheses of `nh` positions compacted on the
     // device (hmap / hcount), the scorer sized by nh and cut at *hcount
     static hipError_t score_compact(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t nh,
@@ -1948,18 +1927,18 @@ struct FundTraits : GeoTraits {     // up to kFModels models per sample
 };
 
 struct EssTraits : FundTraits {      // up to kEModels models per sample (ess.h)
-    static constexpr size_t kPer = kEModels;
+    static constexpr size_t kPer = kSolverTable[GCR_SOLVER_ESSENTIAL5].per;
 };
 
 struct GravTraits : FundTraits {     // up to kGModels models per sample (grav.h)
-    static constexpr size_t kPer = kGModels;
+    static constexpr size_t kPer = kSolverTable[GCR_SOLVER_ESSENTIAL3_GRAVITY].per;
 };
 
 // Homography from two SIFT correspondences: up to kSModels models per sample
-// (sifth.h), compacted as the fundamental matrix's are; P->dp.solver is 3, so
-// every scorer, mask and the fit are the homography's
+// (sifth.h), compacted as the fundamental matrix's are; its kind is the
+// homography's, and so are every scorer, mask and the fit
 struct SiftHTraits : FundTraits {
-    static constexpr size_t kPer = kSModels;
+    static constexpr size_t kPer = kSolverTable[GCR_SOLVER_HOMOGRAPHY2_SIFT].per;
 };
 
 constexpr int kMaxLOSample = 64;     // largest LO sample: 7 x the largest minimal sample (7)
@@ -3090,7 +3069,7 @@ private:
         if constexpr (kRect) {
             if (!exact_) return b;
             b.slot = slot;
-            b.inc = (P_->solver == 2 && inc >= 1 && inc <= 101) ? inc : 0;
+            b.inc = (P_->solver == GCR_SOLVER_SIFT22 && inc >= 1 && inc <= 101) ? inc : 0;
             b.exact = fl == 0 && !unsafe(m);
         }
         return b;
@@ -3098,7 +3077,8 @@ private:
     // the model the reference holds for a generated hypothesis (glibc phi)
     Model dec_of(const Model& m, uint64_t slot, uint32_t inc) const {
         if constexpr (kRect) {
-            if (P_->solver == 2 && inc >= 1 && inc <= 101) return glibc_minimal_model(P_, prm_.seed, slot, inc - 1, m);
+            if (P_->solver == GCR_SOLVER_SIFT22 && inc >= 1 && inc <= 101)
+                return glibc_minimal_model(P_, prm_.seed, slot, inc - 1, m);
         }
         return m;
     }
@@ -3209,7 +3189,7 @@ private:
     bool use_graph() {
         if (graph_state_ < 0) {
             graph_state_ = 0;
-            if (P_->solver >= 3 && prm_.cell_number > 0 && prm_.spatial_coherence_weight > 0) {
+            if (solver_row(P_->solver).corr && prm_.cell_number > 0 && prm_.spatial_coherence_weight > 0) {
                 const HostClass& c = P_->hc[0];
                 // essential matrix: the grid lies over the pixels
                 const bool px = is_ess(P_->solver);
@@ -4362,11 +4342,19 @@ private:
 };
 
 using Runner = RunnerT<RectTraits>;
-using GeoRunner = RunnerT<GeoTraits>;
-using FundRunner = RunnerT<FundTraits>;
-using EssRunner = RunnerT<EssTraits>;
-using GravRunner = RunnerT<GravTraits>;
-using SiftHRunner = RunnerT<SiftHTraits>;
+
+// go(the problem's runner): the one place that maps a solver to its RunnerT
+template <class F>
+int with_runner(gcr_problem* prob, const gcr_params& prm, F&& go) {
+    switch (prob->solver) {
+        case GCR_SOLVER_HOMOGRAPHY2_SIFT: return go(RunnerT<SiftHTraits>(prob, prm));
+        case GCR_SOLVER_ESSENTIAL3_GRAVITY: return go(RunnerT<GravTraits>(prob, prm));
+        case GCR_SOLVER_ESSENTIAL5: return go(RunnerT<EssTraits>(prob, prm));
+        case GCR_SOLVER_FUNDAMENTAL7: return go(RunnerT<FundTraits>(prob, prm));
+        case GCR_SOLVER_HOMOGRAPHY4: return go(RunnerT<GeoTraits>(prob, prm));
+        default: return go(Runner(prob, prm));
+    }
+}
 
 }  // namespace
 
@@ -4391,7 +4379,7 @@ int check_params(const gcr_params* p, int solver) {
     if (!(p->confidence > 0.0 && p->confidence < 1.0))
         return set_err(GCR_EINVAL, "confidence must be in (0, 1)");
     if (p->cell_number > 0) {
-        if (solver < 3)
+        if (solver < GCR_SOLVER_HOMOGRAPHY4)
             return set_err(GCR_EINVAL, "a neighbourhood grid is only supported for the homography and fundamental "
                                        "matrix estimators (the rectification entry points use an empty grid)");
         for (int d = 0; d < 4; ++d)
@@ -4539,6 +4527,75 @@ BatchCtxPool& batch_ctx_pool() {
 }
 }  // namespace
 
+// ------------------------------------------- host twins, written once ----
+// Rows idx[0 .. M) of N x 4 correspondences as the solvers' coordinate arrays.
+template <int M>
+static void load_rows(const double* correspondences, const uint32_t* idx, double* x1, double* y1, double* x2,
+                      double* y2) {
+    for (int j = 0; j < M; ++j) {
+        const double* r = correspondences + 4 * (size_t)idx[j];
+        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
+    }
+}
+
+// The host twin of a correspondence generator (k_generate_e / _g / _s), slot
+// by slot over `threads` host threads: attempts 0..100, the first success
+// wins.  An attempt draws M indices of n rows -- guided with gt, else uniform
+// -- and solve(idx, ms) returns its 0 .. NMODELS models.  inc_out / models_out
+// as gcr_debug_generate_h's.
+template <int M, int NMODELS, class Solve>
+static int host_generate(size_t n, const GuidedTable* gt, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
+                         uint8_t* inc_out, double* models_out, Solve solve) {
+    threads = std::min(std::max(threads, 1), 256);
+    return guard([&]() -> int {
+        auto work = [&](uint32_t lo, uint32_t hi) {
+            for (uint32_t s = lo; s < hi; ++s) {
+                uint8_t* oi = inc_out + (size_t)NMODELS * s;
+                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)NMODELS * s;
+                int cnt = 0;
+                uint32_t a = 0;
+                GeoModel ms[NMODELS];
+                for (; a < 101 && cnt == 0; ++a) {
+                    uint32_t idx[M];
+                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
+                    const bool drawn = gt != nullptr ? sample_guided<M>(ws, *gt, gt->coarse, M, idx)
+                                                     : sample_distinct<M>(ws, n, M, idx);
+                    if (drawn) cnt = solve(idx, ms);
+                }
+                for (int q = 0; q < NMODELS; ++q) {
+                    out[q] = q < cnt ? ms[q] : default_geo();
+                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
+                }
+            }
+        };
+        std::vector<std::thread> pool;
+        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
+        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
+        work(0, std::min(nslots, step));
+        for (auto& t : pool) t.join();
+        return GCR_OK;
+    });
+}
+
+// The four gcr_host_fit_* hooks of the correspondence estimators: the listed
+// rows' non-minimal fit, fit(class, list, model), on classes filled for `kind`.
+template <class Fit>
+static int host_fit_corr(int kind, const double* correspondences, size_t n, const uint32_t* idx, size_t k,
+                         double* model_out, Fit fit) {
+    if (!correspondences || !idx || !model_out) return set_err(GCR_EINVAL, "bad arguments");
+    return guard([&]() -> int {
+        HostClass hc[2];
+        fill_host_classes(kind, correspondences, n, nullptr, 0, hc);
+        std::vector<uint32_t> list(idx, idx + k);
+        for (uint32_t i : list)
+            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
+        GeoModel m;
+        if (!fit(hc[0], list, m)) return 0;
+        for (int q = 0; q < 9; ++q) model_out[q] = m.h[q];
+        return 1;
+    });
+}
+
 extern "C" {
 
 const char* gcr_last_error(void) { return g_err.c_str(); }
@@ -4655,11 +4712,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
             fill_stats(stats_out, r.stats());
             return total;
         };
-        if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
-        return prob->solver == GCR_SOLVER_HOMOGRAPHY4 ? go(GeoRunner(prob, *params)) : go(Runner(prob, *params));
+        return with_runner(prob, *params, go);
     });
 }
 
@@ -4681,12 +4734,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
             fill_stats(stats_out, r.stats());
             return total;
         };
-        if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
-        return go(Runner(prob, *params));
+        return with_runner(prob, *params, go);
     });
 }
 
@@ -4763,12 +4811,7 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
             return total;
         };
         try {
-            if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
-            if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
-            if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
-            if (prob->solver == GCR_SOLVER_HOMOGRAPHY4) return go(GeoRunner(prob, *params));
-            return go(Runner(prob, *params));
+            return with_runner(prob, *params, go);
         } catch (...) {
             // An error on this rank (a HIP or RCCL failure, a peer's failure
             // seen by comm_sync, bad input found mid-run): the other ranks
@@ -4799,11 +4842,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
             fill_stats(stats_out, r.stats());
             return GCR_OK;
         };
-        if (prob->solver == GCR_SOLVER_HOMOGRAPHY2_SIFT) return go(SiftHRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL3_GRAVITY) return go(GravRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_ESSENTIAL5) return go(EssRunner(prob, *params));
-        if (prob->solver == GCR_SOLVER_FUNDAMENTAL7) return go(FundRunner(prob, *params));
-        return prob->solver == GCR_SOLVER_HOMOGRAPHY4 ? go(GeoRunner(prob, *params)) : go(Runner(prob, *params));
+        return with_runner(prob, *params, go);
     });
 }
 
@@ -4994,58 +5033,19 @@ int gcr_host_essential_normalise(const double* correspondences, size_t n, const 
 
 int gcr_host_generate_e(const double* correspondences, size_t n, uint64_t seed, uint64_t slot0, uint32_t nslots,
                         int threads, uint8_t* inc_out, double* models_out) {
+    constexpr SolverRow row = kSolverTable[GCR_SOLVER_ESSENTIAL5];
     if (!correspondences || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
-    if (n < 5 || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
-    if (threads < 1) threads = 1;
-    if (threads > 256) threads = 256;
-    return guard([&]() -> int {
-        // k_generate_e's rule, slot by slot: attempts 0..100, the first success wins
-        auto work = [&](uint32_t lo, uint32_t hi) {
-            for (uint32_t s = lo; s < hi; ++s) {
-                uint8_t* oi = inc_out + (size_t)kEModels * s;
-                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)kEModels * s;
-                int cnt = 0;
-                uint32_t a = 0;
-                GeoModel ms[kEModels];
-                for (; a < 101 && cnt == 0; ++a) {
-                    uint32_t idx[5];
-                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
-                    if (!sample_distinct<5>(ws, n, 5, idx)) continue;
-                    double x1[5], y1[5], x2[5], y2[5];
-                    for (int j = 0; j < 5; ++j) {
-                        const double* r = correspondences + 4 * (size_t)idx[j];
-                        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
-                    }
-                    cnt = solve_e5(x1, y1, x2, y2, ms);
-                }
-                for (int q = 0; q < kEModels; ++q) {
-                    out[q] = q < cnt ? ms[q] : default_geo();
-                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
-                }
-            }
-        };
-        std::vector<std::thread> pool;
-        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
-        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
-        work(0, std::min(nslots, step));
-        for (auto& t : pool) t.join();
-        return GCR_OK;
-    });
+    if (n < (size_t)row.m || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
+    return host_generate<row.m, row.per>(n, nullptr, seed, slot0, nslots, threads, inc_out, models_out,
+                                         [&](const uint32_t* idx, GeoModel* ms) {
+                                             double x1[row.m], y1[row.m], x2[row.m], y2[row.m];
+                                             load_rows<row.m>(correspondences, idx, x1, y1, x2, y2);
+                                             return solve_e5(x1, y1, x2, y2, ms);
+                                         });
 }
 
 int gcr_host_fit_e(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* E_out) {
-    if (!correspondences || !idx || !E_out) return set_err(GCR_EINVAL, "bad arguments");
-    return guard([&]() -> int {
-        HostClass hc[2];
-        fill_host_classes(GCR_SOLVER_FUNDAMENTAL7, correspondences, n, nullptr, 0, hc);
-        std::vector<uint32_t> list(idx, idx + k);
-        for (uint32_t i : list)
-            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
-        GeoModel m;
-        if (!fit_e5_nonminimal(hc[0], list, m)) return 0;
-        for (int q = 0; q < 9; ++q) E_out[q] = m.h[q];
-        return 1;
-    });
+    return host_fit_corr(kKindFundamental, correspondences, n, idx, k, E_out, fit_e5_nonminimal);
 }
 
 // ---- essential matrix with known gravity (grav.h) -------------------------
@@ -5092,11 +5092,9 @@ int gcr_host_solve_g3(const double* correspondences, size_t n, const uint32_t* i
     GravRot rot;
     if (!load_rot(G1, G2, rot)) return GCR_EINVAL;
     double x1[3], y1[3], x2[3], y2[3];
-    for (int j = 0; j < 3; ++j) {
+    for (int j = 0; j < 3; ++j)
         if (idx[j] >= n) return set_err(GCR_EINVAL, "index out of range");
-        const double* r = correspondences + 4 * (size_t)idx[j];
-        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
-    }
+    load_rows<3>(correspondences, idx, x1, y1, x2, y2);
     // kernels.hip attempt_g: normalised rows, up to kGModels models
     GeoModel ms[kGModels];
     const int cnt = solve_g3(x1, y1, x2, y2, rot, ms);
@@ -5109,51 +5107,21 @@ int gcr_host_solve_g3(const double* correspondences, size_t n, const uint32_t* i
 int gcr_host_generate_g(const double* correspondences, size_t n, const double* G1, const double* G2,
                         const double* probabilities, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
                         uint8_t* inc_out, double* models_out) {
+    constexpr SolverRow row = kSolverTable[GCR_SOLVER_ESSENTIAL3_GRAVITY];
     if (!correspondences || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
-    if (n < 3 || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
+    if (n < (size_t)row.m || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
     GravRot rot;
     if (!load_rot(G1, G2, rot)) return GCR_EINVAL;
     std::vector<double> tab;
     GuidedTable gt{};
     if (probabilities != nullptr)
-        if (int e = build_guided(probabilities, n, 3, tab, gt)) return e;
-    if (threads < 1) threads = 1;
-    if (threads > 256) threads = 256;
-    return guard([&]() -> int {
-        // k_generate_g's rule, slot by slot: attempts 0..100, the first success wins
-        auto work = [&](uint32_t lo, uint32_t hi) {
-            for (uint32_t s = lo; s < hi; ++s) {
-                uint8_t* oi = inc_out + (size_t)kGModels * s;
-                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)kGModels * s;
-                int cnt = 0;
-                uint32_t a = 0;
-                GeoModel ms[kGModels];
-                for (; a < 101 && cnt == 0; ++a) {
-                    uint32_t idx[3];
-                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
-                    const bool drawn = probabilities != nullptr ? sample_guided<3>(ws, gt, gt.coarse, 3, idx)
-                                                                : sample_distinct<3>(ws, n, 3, idx);
-                    if (!drawn) continue;
-                    double x1[3], y1[3], x2[3], y2[3];
-                    for (int j = 0; j < 3; ++j) {
-                        const double* r = correspondences + 4 * (size_t)idx[j];
-                        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
-                    }
-                    cnt = solve_g3(x1, y1, x2, y2, rot, ms);
-                }
-                for (int q = 0; q < kGModels; ++q) {
-                    out[q] = q < cnt ? ms[q] : default_geo();
-                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
-                }
-            }
-        };
-        std::vector<std::thread> pool;
-        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
-        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
-        work(0, std::min(nslots, step));
-        for (auto& t : pool) t.join();
-        return GCR_OK;
-    });
+        if (int e = build_guided(probabilities, n, row.m, tab, gt)) return e;
+    return host_generate<row.m, row.per>(n, probabilities != nullptr ? &gt : nullptr, seed, slot0, nslots, threads,
+                                         inc_out, models_out, [&](const uint32_t* idx, GeoModel* ms) {
+                                             double x1[row.m], y1[row.m], x2[row.m], y2[row.m];
+                                             load_rows<row.m>(correspondences, idx, x1, y1, x2, y2);
+                                             return solve_g3(x1, y1, x2, y2, rot, ms);
+                                         });
 }
 
 int gcr_host_fit_g(const double* correspondences, size_t n, const uint32_t* idx, size_t k, const double* G1,
@@ -5161,17 +5129,10 @@ int gcr_host_fit_g(const double* correspondences, size_t n, const uint32_t* idx,
     if (!correspondences || !idx || !E_out) return set_err(GCR_EINVAL, "bad arguments");
     GravRot rot;
     if (!load_rot(G1, G2, rot)) return GCR_EINVAL;
-    return guard([&]() -> int {
-        HostClass hc[2];
-        fill_host_classes(GCR_SOLVER_FUNDAMENTAL7, correspondences, n, nullptr, 0, hc);
-        std::vector<uint32_t> list(idx, idx + k);
-        for (uint32_t i : list)
-            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
-        GeoModel m;
-        if (!fit_g3_nonminimal(hc[0], list, rot, m)) return 0;
-        for (int q = 0; q < 9; ++q) E_out[q] = m.h[q];
-        return 1;
-    });
+    return host_fit_corr(kKindFundamental, correspondences, n, idx, k, E_out,
+                         [&](const HostClass& c, const std::vector<uint32_t>& list, GeoModel& m) {
+                             return fit_g3_nonminimal(c, list, rot, m);
+                         });
 }
 
 // ---- homography from two SIFT correspondences (sifth.h) -------------------
@@ -5199,9 +5160,8 @@ int gcr_host_check_sift(const double* sift, size_t n) { return check_sift(sift, 
 // rows idx[0], idx[1] as sifth.h's sample
 static void load_sift_sample(const double* correspondences, const double* sift, const uint32_t idx[2], double x1[2],
                              double y1[2], double x2[2], double y2[2], SiftPair& sp) {
+    load_rows<2>(correspondences, idx, x1, y1, x2, y2);
     for (int j = 0; j < 2; ++j) {
-        const double* r = correspondences + 4 * (size_t)idx[j];
-        x1[j] = r[0]; y1[j] = r[1]; x2[j] = r[2]; y2[j] = r[3];
         double v[5];
         sift_row(sift + 4 * (size_t)idx[j], v);
         sp.r[j] = v[0]; sp.c1[j] = v[1]; sp.s1[j] = v[2]; sp.c2[j] = v[3]; sp.s2[j] = v[4];
@@ -5230,63 +5190,25 @@ int gcr_host_solve_s2(const double* correspondences, const double* sift, size_t 
 int gcr_host_generate_s(const double* correspondences, const double* sift, size_t n, const double* probabilities,
                         uint64_t seed, uint64_t slot0, uint32_t nslots, int threads, uint8_t* inc_out,
                         double* models_out) {
+    constexpr SolverRow row = kSolverTable[GCR_SOLVER_HOMOGRAPHY2_SIFT];
     if (!correspondences || !sift || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
-    if (n < 2 || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
+    if (n < (size_t)row.m || n > 0xffffffffull) return set_err(GCR_EINVAL, "bad number of correspondences");
     if (int e = check_sift(sift, n)) return e;
     std::vector<double> tab;
     GuidedTable gt{};
     if (probabilities != nullptr)
-        if (int e = build_guided(probabilities, n, 2, tab, gt)) return e;
-    if (threads < 1) threads = 1;
-    if (threads > 256) threads = 256;
-    return guard([&]() -> int {
-        // k_generate_s's rule, slot by slot: attempts 0..100, the first success wins
-        auto work = [&](uint32_t lo, uint32_t hi) {
-            for (uint32_t s = lo; s < hi; ++s) {
-                uint8_t* oi = inc_out + (size_t)kSModels * s;
-                GeoModel* out = reinterpret_cast<GeoModel*>(models_out) + (size_t)kSModels * s;
-                int cnt = 0;
-                uint32_t a = 0;
-                GeoModel ms[kSModels];
-                for (; a < 101 && cnt == 0; ++a) {
-                    uint32_t idx[2];
-                    WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
-                    const bool drawn = probabilities != nullptr ? sample_guided<2>(ws, gt, gt.coarse, 2, idx)
-                                                                : sample_distinct<2>(ws, n, 2, idx);
-                    if (!drawn) continue;
-                    double x1[2], y1[2], x2[2], y2[2];
-                    SiftPair sp;
-                    load_sift_sample(correspondences, sift, idx, x1, y1, x2, y2, sp);
-                    cnt = solve_s2(x1, y1, x2, y2, sp, ms);
-                }
-                for (int q = 0; q < kSModels; ++q) {
-                    out[q] = q < cnt ? ms[q] : default_geo();
-                    oi[q] = q == 0 ? (uint8_t)(cnt > 0 ? a : 102) : (q < cnt ? 0 : 255);
-                }
-            }
-        };
-        std::vector<std::thread> pool;
-        const uint32_t step = (nslots + (uint32_t)threads - 1) / (uint32_t)threads;
-        for (uint32_t lo = step; lo < nslots; lo += step) pool.emplace_back(work, lo, std::min(nslots, lo + step));
-        work(0, std::min(nslots, step));
-        for (auto& t : pool) t.join();
-        return GCR_OK;
-    });
+        if (int e = build_guided(probabilities, n, row.m, tab, gt)) return e;
+    return host_generate<row.m, row.per>(n, probabilities != nullptr ? &gt : nullptr, seed, slot0, nslots, threads,
+                                         inc_out, models_out, [&](const uint32_t* idx, GeoModel* ms) {
+                                             double x1[2], y1[2], x2[2], y2[2];
+                                             SiftPair sp;
+                                             load_sift_sample(correspondences, sift, idx, x1, y1, x2, y2, sp);
+                                             return solve_s2(x1, y1, x2, y2, sp, ms);
+                                         });
 }
 
 int gcr_host_fit_f(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* F_out) {
-    if (!correspondences || !idx || !F_out) return set_err(GCR_EINVAL, "bad arguments");
-    return guard([&]() -> int {
-        HostClass hc[2];
-        fill_host_classes(GCR_SOLVER_FUNDAMENTAL7, correspondences, n, nullptr, 0, hc);
-        std::vector<uint32_t> list(idx, idx + k);
-        for (uint32_t i : list)
-            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
-        GeoModel m;
-        if (!fit_f8_nonminimal(hc[0], list, m)) return 0;
-        for (int q = 0; q < 9; ++q) F_out[q] = m.h[q];
-        return 1;
-    });
+    return host_fit_corr(kKindFundamental, correspondences, n, idx, k, F_out, fit_f8_nonminimal);
 }
 
 // ------------------------------------------------------- homography debug ----
@@ -5302,8 +5224,8 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->inc.ensure(nh);
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided(),
-                                 prob->grav(), prob->sift()));
+        HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s,
+                                 prob->guided(), prob->grav(), prob->sift()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -5323,7 +5245,7 @@ int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_
         DevBuf<uint32_t> out;
         out.ensure(std::max<size_t>(cnt, 1));
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_debug_sample(prob->gen_dp(), seed, slot0, nslots, attempt, out.p, s, prob->guided()));
+        HIPC(launch_debug_sample(prob->solver, prob->dp, seed, slot0, nslots, attempt, out.p, s, prob->guided()));
         HIPC(hipMemcpyAsync(idx_out, out.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
         return GCR_OK;
@@ -5343,11 +5265,11 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
         // one untimed launch first (code object load, caches)
-        HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s, prob->guided(),
-                                 prob->grav(), prob->sift()));
+        HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s,
+                                 prob->guided(), prob->grav(), prob->sift()));
         HIPC(hipEventRecord(prob->ctx->ev0, s));
         for (int r = 0; r < reps; ++r)
-            HIPC(launch_generate_geo(prob->gen_dp(), seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
+            HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
                                      prob->w->gmodels.p, s, prob->guided(), prob->grav(), prob->sift()));
         HIPC(hipEventRecord(prob->ctx->ev1, s));
         HIPC(hipEventSynchronize(prob->ctx->ev1));
@@ -5489,18 +5411,7 @@ int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const d
 }
 
 int gcr_host_fit_h(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* H_out) {
-    if (!correspondences || !idx || !H_out) return set_err(GCR_EINVAL, "bad arguments");
-    return guard([&]() -> int {
-        HostClass hc[2];
-        fill_host_classes(GCR_SOLVER_HOMOGRAPHY4, correspondences, n, nullptr, 0, hc);
-        std::vector<uint32_t> list(idx, idx + k);
-        for (uint32_t i : list)
-            if (i >= n) return set_err(GCR_EINVAL, "index out of range");
-        GeoModel m;
-        if (!fit_h4_nonminimal(hc[0], list, m)) return 0;
-        for (int q = 0; q < 9; ++q) H_out[q] = m.h[q];
-        return 1;
-    });
+    return host_fit_corr(kKindHomography, correspondences, n, idx, k, H_out, fit_h4_nonminimal);
 }
 
 // ---------------------------------------------------------------- debug ----
@@ -5576,7 +5487,8 @@ int gcr_debug_score(gcr_problem* prob, const gcr_params* params, const gcr_rect_
 int gcr_debug_verify_slots(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
                            uint8_t* inc_out, uint32_t* n0, uint32_t* n1, double* v0, double* v1, double* tot) {
     if (!prob || !inc_out || !n0 || !n1 || !v0 || !v1 || !tot) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver > 2) return set_err(GCR_EINVAL, "gcr_debug_verify_slots: rectification solvers only");
+    if (!solver_row(prob->solver).rect)
+        return set_err(GCR_EINVAL, "gcr_debug_verify_slots: rectification solvers only");
     if (int e = check_params(params, prob->solver)) return e;
     if (nslots == 0) return set_err(GCR_EINVAL, "nslots must be > 0");
     return guard([&]() -> int {
@@ -5634,7 +5546,7 @@ size_t gcr_debug_exchange_log(uint64_t* out, size_t cap) {
 int gcr_debug_score_less(gcr_problem* prob, const gcr_params* params, const gcr_rect_model* a,
                          const gcr_rect_model* b) {
     if (!prob || !a || !b) return set_err(GCR_EINVAL, "null argument");
-    if (prob->solver > 2) return set_err(GCR_EINVAL, "gcr_debug_score_less: rectification solvers only");
+    if (!solver_row(prob->solver).rect) return set_err(GCR_EINVAL, "gcr_debug_score_less: rectification solvers only");
     if (int e = check_params(params, prob->solver)) return e;
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
@@ -5679,15 +5591,16 @@ int gcr_debug_mask(gcr_problem* prob, const gcr_params* params, const gcr_rect_m
 
 int gcr_host_fit_nonminimal(int solver, const double* f0, size_t n0, const double* f1, size_t n1, const uint32_t* idx0,
                             size_t k0, const uint32_t* idx1, size_t k1, gcr_rect_model* model_out) {
-    if (solver < 0 || solver > 2 || !f0 || !idx0 || !model_out || (solver == 2 && (!f1 || !idx1)))
+    const int K = solver_row(solver).classes;
+    if (!solver_row(solver).rect || !f0 || !idx0 || !model_out || (K == 2 && (!f1 || !idx1)))
         return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
         HostClass hc[2];
         fill_host_classes(solver, f0, n0, f1, n1, hc);
         std::vector<uint32_t> lists[2];
         lists[0].assign(idx0, idx0 + k0);
-        if (solver == 2) lists[1].assign(idx1, idx1 + k1);
-        for (int c = 0; c < (solver == 2 ? 2 : 1); ++c)
+        if (K == 2) lists[1].assign(idx1, idx1 + k1);
+        for (int c = 0; c < K; ++c)
             for (uint32_t i : lists[c])
                 if (i >= hc[c].n) return set_err(GCR_EINVAL, "index out of range");
         RectModel m;
@@ -5699,13 +5612,13 @@ int gcr_host_fit_nonminimal(int solver, const double* f0, size_t n0, const doubl
 
 int gcr_debug_fit_nonminimal(gcr_problem* prob, const uint32_t* idx0, size_t k0, const uint32_t* idx1, size_t k1,
                               int use_gpu, gcr_rect_model* model_out) {
-    if (!prob || !idx0 || !model_out || (prob->solver == 2 && !idx1)) return set_err(GCR_EINVAL, "bad arguments");
+    if (!prob || !idx0 || !model_out || (prob->K == 2 && !idx1)) return set_err(GCR_EINVAL, "bad arguments");
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
         await_spec(prob->w);
         std::vector<uint32_t> lists[2];
         lists[0].assign(idx0, idx0 + k0);
-        if (prob->solver == 2) lists[1].assign(idx1, idx1 + k1);
+        if (prob->K == 2) lists[1].assign(idx1, idx1 + k1);
         for (int c = 0; c < prob->K; ++c)
             for (uint32_t i : lists[c])
                 if (i >= prob->hc[c].n) return set_err(GCR_EINVAL, "index out of range");
@@ -5727,16 +5640,17 @@ double gcr_host_pow_m3(double t) { return dm::dm_pow_m3(t); }
 double gcr_host_atan2(double y, double x) { return dm::dm_atan2(y, x); }
 int gcr_host_residuals(int solver, int cls, const double* features, size_t n, const gcr_rect_model* model, int arith,
                        double* r2_out) {
-    if (solver < 0 || solver > 2 || cls < 0 || cls > (solver == 2 ? 1 : 0) || !model || (n && (!features || !r2_out)))
+    if (!solver_row(solver).rect || cls < 0 || cls >= solver_row(solver).classes || !model ||
+        (n && (!features || !r2_out)))
         return set_err(GCR_EINVAL, "bad residual request");
     return guard([&]() -> int {
         gcr_problem P;
         P.solver = solver;
-        P.K = solver == 2 ? 2 : 1;
+        P.K = solver_row(solver).classes;
         // the features as class `cls` (fill_host_classes: glibc pow / sincos)
         fill_host_classes(solver, features, cls == 0 ? n : 0, features, cls == 1 ? n : 0, P.hc);
         const RectModel m{model->x0, model->y0, model->s, model->h7, model->h8, model->alpha, model->phi};
-        const ValueConst vc = value_const(m, solver == 1, cls == 1);
+        const ValueConst vc = value_const(m, solver == GCR_SOLVER_SCALE3_ORIGINAL, cls == 1);
         for (size_t i = 0; i < n; ++i)
             r2_out[i] = arith == 0 ? host_value(&P, cls, i, m, vc) : host_r2<GlibcMath>(&P, cls, i, m);
         return GCR_OK;

@@ -51,6 +51,7 @@
 // unaffected unless their scores tie to that level.
 #pragma once
 
+#include "gcr.h"
 #include "gcr_hd.h"
 
 namespace gcr {
@@ -169,7 +170,7 @@ inline bool scale_unsafe(int solver, double alpha, double T0, bool scales_ok) {
     if (!(rT < 60.0) || !scales_ok) return true;
     const double ac = (alpha * alpha) * alpha;
     if (!(ac >= 0x1p-200 && ac <= 0x1p200)) return true;
-    const double at_cut = fabs(log(solver == 1 ? 1e-9 / ac : ac * 1e-9));
+    const double at_cut = fabs(log(solver == GCR_SOLVER_SCALE3_ORIGINAL ? 1e-9 / ac : ac * 1e-9));
     return !(at_cut > rT + 1e-3);
 }
 // the problem-level half of it: every positive finite scale feature in

@@ -370,14 +370,14 @@ bool fit_sift22(const HostClass* cls, const std::vector<uint32_t>* idx, RectMode
 
 bool fit_nonminimal(int solver, const HostClass* cls, const std::vector<uint32_t>* idx, RectModel& out,
                     SiftSystemSolver* big, size_t big_rows) {
-    const int K = (solver == 2) ? 2 : 1;
-    const size_t m[2] = {solver == 2 ? 2u : 3u, 2u};
+    const int K = solver_row(solver).classes;
+    const size_t m[2] = {(size_t)solver_row(solver).m, 2u};
     for (int c = 0; c < K; ++c)
         if (idx[c].size() < m[c]) return false;
     if (!normalize_ok(K, cls, idx)) return false;
     bool ok;
-    if (solver == 2) ok = fit_sift22(cls, idx, out, big, big_rows);
-    else ok = fit_scale3(solver == 1, cls[0], idx[0], out);
+    if (solver == GCR_SOLVER_SIFT22) ok = fit_sift22(cls, idx, out, big, big_rows);
+    else ok = fit_scale3(solver == GCR_SOLVER_SCALE3_ORIGINAL, cls[0], idx[0], out);
     if (ok) { out.x0 = 0.0; out.y0 = 0.0; out.s = 1.0; }
     return ok;
 }

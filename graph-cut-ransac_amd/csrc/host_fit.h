@@ -17,6 +17,7 @@
 #include "gram.h"
 #include "grav.h"
 #include "rect.h"
+#include "solver.h"
 
 namespace gcr {
 

@@ -10,6 +10,7 @@
 #include "gram.h"
 #include "guided.h"
 #include "rect.h"
+#include "solver.h"
 #include "summary.h"
 
 namespace gcr {
@@ -62,10 +63,11 @@ struct SmallScratch {
 };
 
 struct DevProblem {
-    int solver;     // GCR_SOLVER_*
+    int kind;       // the residual kind the classes are filled for (solver.h), not the estimator
     DevClass cls[2];
     SmallScratch lo;
 };
+static_assert(sizeof(DevProblem) == 208, "DevProblem is a kernel argument: its layout is fixed");
 
 // Raw MSAC accumulators per hypothesis (host finishes the score exactly as
 // MSACScoringFunction::getScore does, MSAC_scoring_function.hpp:108-127).
@@ -282,30 +284,26 @@ hipError_t launch_select_batches(const WgBest* wg, size_t wg_stride, const RectM
 // true when launch_verify_fused at this batch size uses the chained kernel
 bool verify_chains(uint32_t nslots);
 
-// homography (solver 3) counterparts of launch_generate / launch_score /
-// launch_mask / launch_select
-// solver 3 (homography): one hypothesis per slot; solver 4 (fundamental
-// matrix): kFModels hypotheses per slot (inc / models sized kFModels * nslots,
-// see k_generate_f).  Score / mask / select dispatch on the same solver.
+// The correspondence estimators' counterparts of launch_generate /
+// launch_score / launch_mask / launch_select.  `solver` is the estimator
+// (a correspondence solver of solver.h, else hipErrorInvalidValue), p.kind the
+// residual its scorers and masks dispatch on; inc / models hold the solver's
+// `per` hypotheses per slot (see k_generate_f).
 // guided != nullptr: samples are drawn with the table's probabilities
 // (guided.h) by the generators' guided instantiations; the table goes to the
 // generator launches alone, DevProblem does not carry it.
-// solver 6 (essential matrix with known gravity, grav.h): kGModels hypotheses
-// per slot, and `grav` holds the two rotations (required for this solver,
-// nullptr for the others).
-// solver 7 (homography from two SIFT correspondences, sifth.h): kSModels
-// hypotheses per slot, and `sift` holds the device pointers of the stored SIFT
-// columns (required for this solver, nullptr for the others); p's classes,
-// scorers and masks are the homography's.
-struct GravRot;
-struct SiftCols;
-hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
-                               GeoModel* models, hipStream_t stream, const GuidedTable* guided = nullptr,
-                               const GravRot* grav = nullptr, const SiftCols* sift = nullptr);
-// The generators' sampling function alone (tests): the 4 / 7 indices of
+// grav: the two gravity rotations (grav.h), sift: the device pointers of the
+// stored SIFT columns (sifth.h) -- each required by the solver whose row has
+// needs_gravity / needs_sift and nullptr for the others.
+hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
+                               uint8_t* inc, GeoModel* models, hipStream_t stream,
+                               const GuidedTable* guided = nullptr, const GravRot* grav = nullptr,
+                               const SiftCols* sift = nullptr);
+// The generators' sampling function alone (tests): the solver's m indices of
 // attempt `attempt` of each slot into out, all-ones where the draw budget ran out.
-hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
-                               uint32_t* out, hipStream_t stream, const GuidedTable* guided = nullptr);
+hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
+                               uint32_t attempt, uint32_t* out, hipStream_t stream,
+                               const GuidedTable* guided = nullptr);
 // Hypotheses per workgroup of the batch scorers at a launch of nh (64, 16 or
 // 4; GCR_SPLIT_H pins one for sweeps).
 int split_h(uint32_t nh);

@@ -3636,7 +3636,7 @@ __global__ __launch_bounds__(kSelectThreads) void k_select(int solver, ScoreOut 
     __shared__ uint32_t s_idx[kSelectThreads];
     __shared__ unsigned long long s_models[kSelectThreads], s_its[kSelectThreads];
     const int t = threadIdx.x;
-    const int K = solver == 2 ? 2 : 1;
+    const int K = solver_classes(solver);
     double best = 0.0;
     uint32_t bi = 0xffffffffu;
     unsigned long long nm = 0, its = 0;
@@ -3656,7 +3656,8 @@ __global__ __launch_bounds__(kSelectThreads) void k_select(int solver, ScoreOut 
         }
         if (zero) sum = 0.0;
         bool valid = true;
-        if constexpr (std::is_same<M, RectModel>::value) valid = solver != 2 || valid_model_sift22(models[hyp]);
+        if constexpr (std::is_same<M, RectModel>::value)
+            valid = solver != GCR_SOLVER_SIFT22 || valid_model_sift22(models[hyp]);
         if (best < sum && valid) {
             best = sum;
             bi = j;
@@ -4730,9 +4731,9 @@ template <int G>
 void launch_generate_g(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
                        RectModel* models, hipStream_t stream) {
     const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL((k_generate<0, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models); break;
-        case 1: hipLaunchKernelGGL((k_generate<1, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_generate<0, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_generate<1, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models); break;
         default: hipLaunchKernelGGL((k_generate<2, G>), grid, block, 0, stream, p, seed, slot0, nslots, inc, models); break;
     }
 }
@@ -4754,9 +4755,9 @@ template <bool kIdentity>
 void launch_score_t(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc, uint32_t nh,
                     const ScoreOut& out, hipStream_t stream) {
     const dim3 grid(blocks_for(nh, kScoreBlock)), block(kScoreBlock);
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL((k_score<0, kIdentity>), grid, block, 0, stream, p, T[0], T[1], flag_band(T), models, inc, nh, out); break;
-        case 1: hipLaunchKernelGGL((k_score<1, kIdentity>), grid, block, 0, stream, p, T[0], T[1], flag_band(T), models, inc, nh, out); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_score<0, kIdentity>), grid, block, 0, stream, p, T[0], T[1], flag_band(T), models, inc, nh, out); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_score<1, kIdentity>), grid, block, 0, stream, p, T[0], T[1], flag_band(T), models, inc, nh, out); break;
         default: hipLaunchKernelGGL((k_score<2, kIdentity>), grid, block, 0, stream, p, T[0], T[1], flag_band(T), models, inc, nh, out); break;
     }
 }
@@ -4777,9 +4778,9 @@ void launch_split_t(const DevProblem& p, const double T[2], const RectModel* mod
     const dim3 grid((nh + H - 1) / H), block(kSplitThreads);
     double band0, tan_tau1;
     band_consts(T, band0, tan_tau1);
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL((k_score_split<0, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, GenArgs{}); break;
-        case 1: hipLaunchKernelGGL((k_score_split<1, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, GenArgs{}); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_score_split<0, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, GenArgs{}); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_score_split<1, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, GenArgs{}); break;
         default: hipLaunchKernelGGL((k_score_split<2, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, GenArgs{}); break;
     }
 }
@@ -4806,9 +4807,9 @@ void launch_fm_t(const DevProblem& p, const double T[2], uint32_t nh, const Scor
     const dim3 grid((nh + H - 1) / H), block(kSplitThreads);
     double band0, tan_tau1;
     band_consts(T, band0, tan_tau1);
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL((k_score_fm<0, H, kGen>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, g); break;
-        case 1: hipLaunchKernelGGL((k_score_fm<1, H, kGen>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, g); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_score_fm<0, H, kGen>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, g); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_score_fm<1, H, kGen>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, g); break;
         default: hipLaunchKernelGGL((k_score_fm<2, H, kGen>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, nh, out, g); break;
     }
 }
@@ -5031,9 +5032,9 @@ void launch_fused_t(const DevProblem& p, const double T[2], uint32_t nh, const S
     const dim3 grid((nh + H - 1) / H), block(kSplitThreads);
     double band0, tan_tau1;
     band_consts(T, band0, tan_tau1);
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL((k_score_split<0, H, R, true>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), nullptr, nullptr, nh, out, g); break;
-        case 1: hipLaunchKernelGGL((k_score_split<1, H, R, true>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), nullptr, nullptr, nh, out, g); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_score_split<0, H, R, true>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), nullptr, nullptr, nh, out, g); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_score_split<1, H, R, true>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), nullptr, nullptr, nh, out, g); break;
         default: hipLaunchKernelGGL((k_score_split<2, H, R, true>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), nullptr, nullptr, nh, out, g); break;
     }
 }
@@ -5170,7 +5171,7 @@ uint32_t lo_cpw(uint32_t nm, uint32_t nchunks) {
 
 size_t small_score_pairs(const DevProblem& p) {
     const uint32_t pad0 = (p.cls[0].n + 63u) & ~63u;
-    const uint32_t pad1 = (p.solver == 2) ? ((p.cls[1].n + 63u) & ~63u) : 0u;
+    const uint32_t pad1 = (p.kind == GCR_SOLVER_SIFT22) ? ((p.cls[1].n + 63u) & ~63u) : 0u;
     return (size_t)pad0 + pad1;
 }
 
@@ -5191,12 +5192,12 @@ hipError_t launch_score_small(const DevProblem& p, const double T[2], const void
         // the split pays where the per-pair arithmetic is heavy (the value
         // formulas); the correspondence estimators' residuals are cheap and
         // their one-kernel launch was faster (F latency A/B, round 4)
-        if (KIND <= 2 && lo_split() && lo_fold_wide() && probe == 0 && ntot <= 2 * kLoBlock && nm <= p.lo.cap_models &&
-            p.lo.vals != nullptr && p.lo.meta != nullptr) {
+        if (solver_row(KIND).rect && lo_split() && lo_fold_wide() && probe == 0 && ntot <= 2 * kLoBlock &&
+            nm <= p.lo.cap_models && p.lo.vals != nullptr && p.lo.meta != nullptr) {
             const dim3 grid((nchunks + kLrThreads / 64 - 1) / (kLrThreads / 64), nm);
             ArgModels am;
             am.n = 0;
-            if (KIND <= 2 && hmodels != nullptr && nm <= kArgModels && lo_argmodels()) {
+            if (solver_row(KIND).rect && hmodels != nullptr && nm <= kArgModels && lo_argmodels()) {
                 std::memcpy(am.m, hmodels, (size_t)nm * sizeof(RectModel));
                 am.n = nm;
             }
@@ -5221,11 +5222,11 @@ hipError_t launch_score_small(const DevProblem& p, const double T[2], const void
             hipLaunchKernelGGL((k_lo_chain<KIND, false>), dim3(nm), dim3(kLoThreads), 0, stream, p, mp, inc, T[0],
                                T[1], pad0, ntot, lb, flag_band(T), flag_band(lb.T), out, probe);
     };
-    switch (p.solver) {
-        case 0: go(std::integral_constant<int, 0>{}); break;
-        case 1: go(std::integral_constant<int, 1>{}); break;
-        case 2: go(std::integral_constant<int, 2>{}); break;
-        case 3: go(std::integral_constant<int, 3>{}); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: go(std::integral_constant<int, 0>{}); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: go(std::integral_constant<int, 1>{}); break;
+        case GCR_SOLVER_SIFT22: go(std::integral_constant<int, 2>{}); break;
+        case kKindHomography: go(std::integral_constant<int, 3>{}); break;
         default: go(std::integral_constant<int, 4>{}); break;
     }
     return hipGetLastError();
@@ -5233,7 +5234,7 @@ hipError_t launch_score_small(const DevProblem& p, const double T[2], const void
 
 bool score_small_splits(const DevProblem& p, uint32_t nm_total) {
     const uint32_t ntot = (uint32_t)small_score_pairs(p);
-    return p.solver <= 2 && lo_split() && lo_fold_wide() && !lo_fused() && probe_bits() == 0 && ntot > 0 &&
+    return solver_row(p.kind).rect && lo_split() && lo_fold_wide() && !lo_fused() && probe_bits() == 0 && ntot > 0 &&
            ntot <= 2 * kLoBlock && nm_total <= p.lo.cap_models && p.lo.vals != nullptr && p.lo.meta != nullptr;
 }
 
@@ -5279,9 +5280,9 @@ hipError_t launch_score_small_part(const DevProblem& p, const double T[2], const
             hipLaunchKernelGGL((k_lo_approx<KIND>), dim3(nm_fold), dim3(kLaThreads), 0, stream, q, pad0, nchunks,
                                out);
     };
-    switch (p.solver) {
-        case 0: go(std::integral_constant<int, 0>{}); break;
-        case 1: go(std::integral_constant<int, 1>{}); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: go(std::integral_constant<int, 0>{}); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: go(std::integral_constant<int, 1>{}); break;
         default: go(std::integral_constant<int, 2>{}); break;
     }
     return hipGetLastError();
@@ -5295,9 +5296,9 @@ hipError_t launch_lo_fold_slots(const DevProblem& p, uint32_t src, uint32_t nm, 
     q.lo.psum = nullptr;
     const uint32_t pad0 = (p.cls[0].n + 63u) & ~63u;
     const uint32_t nchunks = (uint32_t)small_score_pairs(p) / 64;
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL((k_lo_fold<0>), dim3(nm), dim3(kLoThreads), 0, stream, q, pad0, nchunks, out, src, slot); break;
-        case 1: hipLaunchKernelGGL((k_lo_fold<1>), dim3(nm), dim3(kLoThreads), 0, stream, q, pad0, nchunks, out, src, slot); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_lo_fold<0>), dim3(nm), dim3(kLoThreads), 0, stream, q, pad0, nchunks, out, src, slot); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_lo_fold<1>), dim3(nm), dim3(kLoThreads), 0, stream, q, pad0, nchunks, out, src, slot); break;
         default: hipLaunchKernelGGL((k_lo_fold<2>), dim3(nm), dim3(kLoThreads), 0, stream, q, pad0, nchunks, out, src, slot); break;
     }
     return hipGetLastError();
@@ -5310,9 +5311,9 @@ hipError_t launch_mask(const DevProblem& p, int cls, const RectModel& model, int
     const dim3 grid(blocks_for(c.n, kMaskBlock)), block(kMaskBlock);
     double fmid, fhalf;
     flag_band_1(T, cls, fmid, fhalf);
-    switch (p.solver) {
-        case 0: hipLaunchKernelGGL(k_mask<0>, grid, block, 0, stream, c, cls, model, rule, T, lambda, fmid, fhalf, mask); break;
-        case 1: hipLaunchKernelGGL(k_mask<1>, grid, block, 0, stream, c, cls, model, rule, T, lambda, fmid, fhalf, mask); break;
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL(k_mask<0>, grid, block, 0, stream, c, cls, model, rule, T, lambda, fmid, fhalf, mask); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL(k_mask<1>, grid, block, 0, stream, c, cls, model, rule, T, lambda, fmid, fhalf, mask); break;
         default: hipLaunchKernelGGL(k_mask<2>, grid, block, 0, stream, c, cls, model, rule, T, lambda, fmid, fhalf, mask); break;
     }
     return hipGetLastError();
@@ -5407,16 +5408,80 @@ hipError_t launch_math(int op, const double* a, const double* b, size_t n, doubl
     return hipGetLastError();
 }
 
-// ------------------------------------ homography (3) / fundamental (4) ----
-hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint8_t* inc,
-                               GeoModel* models, hipStream_t stream, const GuidedTable* guided,
+// ------------------------------------------ correspondence estimators ----
+// A runtime correspondence solver as a compile-time tag: f gets SolverTag<
+// GCR_SOLVER_*>; false (f not called) for any other value.
+template <int S>
+using SolverTag = std::integral_constant<int, S>;
+template <class F>
+bool with_corr_solver(int solver, F&& f) {
+    switch (solver) {
+        case GCR_SOLVER_HOMOGRAPHY2_SIFT: f(SolverTag<GCR_SOLVER_HOMOGRAPHY2_SIFT>{}); return true;
+        case GCR_SOLVER_ESSENTIAL3_GRAVITY: f(SolverTag<GCR_SOLVER_ESSENTIAL3_GRAVITY>{}); return true;
+        case GCR_SOLVER_ESSENTIAL5: f(SolverTag<GCR_SOLVER_ESSENTIAL5>{}); return true;
+        case GCR_SOLVER_FUNDAMENTAL7: f(SolverTag<GCR_SOLVER_FUNDAMENTAL7>{}); return true;
+        case GCR_SOLVER_HOMOGRAPHY4: f(SolverTag<GCR_SOLVER_HOMOGRAPHY4>{}); return true;
+        default: return false;
+    }
+}
+
+bool guided_table_fits(const GuidedTable* guided, const DevProblem& p) {
+    return guided == nullptr || (guided->n == p.cls[0].n && guided->buckets <= kGuidedCoarse && guided->buckets != 0 &&
+                                 (size_t)guided->stride * guided->buckets >= guided->n);
+}
+
+// lanes per slot of the generators (GCR_GEN_G overrides it, launch_generate_geo)
+int gen_lanes(int solver, uint32_t nslots) {
+    switch (solver) {
+        // 7-point solver: ~7.7 attempts per slot at 80 % outliers (p99 35), latency-
+        // bound per attempt.  Fixed groups (round 1): G = 8 / 16 / 32 / 64 -> 0.46 /
+        // 0.37 / 0.34 / 0.36 ms per 4096-slot step.  Widening groups (F bench line,
+        // 3712 slots, two-stream pipeline, profiles/r2_v8_fwiden.txt): G = 4 / 8 /
+        // 16 / 32 / 64 -> 0.173 / 0.143 / 0.126 / 0.139 / 0.159 ms per step, fixed
+        // G = 32 0.138 ms.  The replay path's large chunks (F wall time to 0.99,
+        // every launch forced, profiles/r2_v13_bconc.txt): G = 2 / 4 / 8 / 16 ->
+        // 8.08 / 7.77 / 7.38 / 7.43 ms
+        case GCR_SOLVER_FUNDAMENTAL7: return nslots <= 8192 ? 16 : 8;
+        // 5-point solver: nearly every attempt yields a model (the solver's own
+        // rank tests and the oriented test are its only failures), so wide groups
+        // would mostly compute attempts that lose to attempt 0
+        case GCR_SOLVER_ESSENTIAL5: return nslots <= 32768 ? 4 : 1;
+        // 3-point gravity solver: 1.34 attempts per slot at 80 % outliers (the
+        // oriented test and quartics without real roots fail the rest), yet a launch
+        // is bound by one wave's serial time (nine short bracket solves per attempt
+        // under divergence) times its rounds, so spare lanes pay as long as every
+        // wave is resident at once (2048 waves: 16 384 slots of 8 lanes).  Per
+        // launch of 1024 / 3712 / 14 848 / 65 536 slots: G = 1 -> 0.251 / 0.278 /
+        // 0.314 / 0.317 ms, 2 -> 0.146 / 0.162 / 0.184 / 0.209, 4 -> 0.091 / 0.097 /
+        // 0.110 / 0.207, 8 -> 0.062 / 0.066 / 0.085 / 0.273, 16 -> 0.062 / 0.067 /
+        // 0.140 / 0.507, 32 -> 0.065 / 0.079 / - / 0.978 (MEASUREMENTS.md; the
+        // choice made by reading the code before these numbers was 2)
+        case GCR_SOLVER_ESSENTIAL3_GRAVITY: return nslots <= 16384 ? 8 : 4;
+        // 2-point SIFT homography solver: 3.3 attempts per slot at 80 % outliers
+        // (3.9 at 95 %: a cubic always has a real root, the failures are the sign
+        // and orientation tests on outlier pairs), each attempt one long serial
+        // chain (the 6 x 9 elimination, the bracket solves), so spare lanes pay
+        // while the waves are resident at once.  Per launch of 1024 / 3712 /
+        // 14 848 / 65 536 slots at 80 % outliers: G = 1 -> 0.466 / 0.520 / 0.571 /
+        // 0.590 ms, 2 -> 0.251 / 0.286 / 0.299 / 0.382, 4 -> 0.142 / 0.152 / 0.162 /
+        // 0.312, 8 -> 0.088 / 0.090 / 0.117 / 0.290, 16 -> 0.052 / 0.056 / 0.109 /
+        // 0.342, 32 -> 0.036 / 0.055 / 0.163 / 0.609 (MEASUREMENTS.md; the choice
+        // made by reading the code before these numbers was the gravity solver's,
+        // 8 up to 16 384 slots and 4 above)
+        case GCR_SOLVER_HOMOGRAPHY2_SIFT: return nslots <= 2048 ? 32 : nslots <= 16384 ? 16 : 8;
+        default: return nslots <= 8192 ? 16 : nslots <= 32768 ? 4 : 1;      // 4-point homography
+    }
+}
+
+hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
+                               uint8_t* inc, GeoModel* models, hipStream_t stream, const GuidedTable* guided,
                                const GravRot* grav, const SiftCols* sift) {
     if (nslots == 0) return hipSuccess;
-    if ((p.solver == 6) != (grav != nullptr)) return hipErrorInvalidValue;
-    if ((p.solver == 7) != (sift != nullptr)) return hipErrorInvalidValue;
-    if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
-                              (size_t)guided->stride * guided->buckets < guided->n))
-        return hipErrorInvalidValue;
+    const SolverRow row = solver_row(solver);
+    if (!row.corr || row.kind != p.kind) return hipErrorInvalidValue;
+    if (row.needs_gravity != (grav != nullptr)) return hipErrorInvalidValue;
+    if (row.needs_sift != (sift != nullptr)) return hipErrorInvalidValue;
+    if (!guided_table_fits(guided, p)) return hipErrorInvalidValue;
     // GCR_GEN_WIDEN=0: the fundamental-matrix generator keeps fixed groups of
     // G lanes per slot (k_generate_f) instead of widening them (k_generate_fw).
     // Both knobs are read per launch (tests switch them in-process).
@@ -5430,29 +5495,32 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
         // t: nothing (the uniform kernels) or the guided table
         auto run = [&](auto... t) {
-            if (p.solver == 7) {
-                hipLaunchKernelGGL((k_generate_s<G, decltype(t)...>), grid, block, 0, stream, p, *sift, seed, slot0,
-                                   nslots, inc, models, t...);
-            } else if (p.solver == 6) {
-                hipLaunchKernelGGL((k_generate_g<G, decltype(t)...>), grid, block, 0, stream, p, *grav, seed, slot0,
-                                   nslots, inc, models, t...);
-            } else if (p.solver == 5) {
-                hipLaunchKernelGGL((k_generate_e<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0, nslots,
-                                   inc, models, t...);
-            } else if (p.solver == 4) {
-                if (widen)
-                    hipLaunchKernelGGL((k_generate_fw<4, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
+            with_corr_solver(solver, [&](auto stag) {
+                constexpr int S = decltype(stag)::value;
+                if constexpr (S == GCR_SOLVER_HOMOGRAPHY2_SIFT) {
+                    hipLaunchKernelGGL((k_generate_s<G, decltype(t)...>), grid, block, 0, stream, p, *sift, seed,
+                                       slot0, nslots, inc, models, t...);
+                } else if constexpr (S == GCR_SOLVER_ESSENTIAL3_GRAVITY) {
+                    hipLaunchKernelGGL((k_generate_g<G, decltype(t)...>), grid, block, 0, stream, p, *grav, seed, slot0,
                                        nslots, inc, models, t...);
-                else
-                    hipLaunchKernelGGL((k_generate_f<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
+                } else if constexpr (S == GCR_SOLVER_ESSENTIAL5) {
+                    hipLaunchKernelGGL((k_generate_e<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
                                        nslots, inc, models, t...);
-            } else if (hwiden) {
-                hipLaunchKernelGGL((k_generate_fw<3, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
-                                   nslots, inc, models, t...);
-            } else {
-                hipLaunchKernelGGL((k_generate<3, G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0, nslots,
-                                   inc, models, t...);
-            }
+                } else if constexpr (S == GCR_SOLVER_FUNDAMENTAL7) {
+                    if (widen)
+                        hipLaunchKernelGGL((k_generate_fw<kKindFundamental, G, decltype(t)...>), grid, block, 0, stream,
+                                           p, seed, slot0, nslots, inc, models, t...);
+                    else
+                        hipLaunchKernelGGL((k_generate_f<G, decltype(t)...>), grid, block, 0, stream, p, seed, slot0,
+                                           nslots, inc, models, t...);
+                } else if (hwiden) {
+                    hipLaunchKernelGGL((k_generate_fw<kKindHomography, G, decltype(t)...>), grid, block, 0, stream, p,
+                                       seed, slot0, nslots, inc, models, t...);
+                } else {
+                    hipLaunchKernelGGL((k_generate<kKindHomography, G, decltype(t)...>), grid, block, 0, stream, p,
+                                       seed, slot0, nslots, inc, models, t...);
+                }
+            });
         };
         if (guided != nullptr) run(*guided);
         else run();
@@ -5460,43 +5528,7 @@ hipError_t launch_generate_geo(const DevProblem& p, uint64_t seed, uint64_t slot
     // GCR_GEN_G overrides the lanes per slot (1 .. 64)
     const char* eg = getenv("GCR_GEN_G");
     const int env_g = eg ? atoi(eg) : 0;
-    // 7-point solver: ~7.7 attempts per slot at 80 % outliers (p99 35), latency-
-    // bound per attempt.  Fixed groups (round 1): G = 8 / 16 / 32 / 64 -> 0.46 /
-    // 0.37 / 0.34 / 0.36 ms per 4096-slot step.  Widening groups (F bench line,
-    // 3712 slots, two-stream pipeline, profiles/r2_v8_fwiden.txt): G = 4 / 8 /
-    // 16 / 32 / 64 -> 0.173 / 0.143 / 0.126 / 0.139 / 0.159 ms per step, fixed
-    // G = 32 0.138 ms.  The replay path's large chunks (F wall time to 0.99,
-    // every launch forced, profiles/r2_v13_bconc.txt): G = 2 / 4 / 8 / 16 ->
-    // 8.08 / 7.77 / 7.38 / 7.43 ms
-    int g = p.solver == 4 ? (nslots <= 8192 ? 16 : 8)
-                          : (nslots <= 8192 ? 16 : nslots <= 32768 ? 4 : 1);
-    // 5-point solver: nearly every attempt yields a model (the solver's own
-    // rank tests and the oriented test are its only failures), so wide groups
-    // would mostly compute attempts that lose to attempt 0
-    if (p.solver == 5) g = nslots <= 32768 ? 4 : 1;
-    // 3-point gravity solver: 1.34 attempts per slot at 80 % outliers (the
-    // oriented test and quartics without real roots fail the rest), yet a launch
-    // is bound by one wave's serial time (nine short bracket solves per attempt
-    // under divergence) times its rounds, so spare lanes pay as long as every
-    // wave is resident at once (2048 waves: 16 384 slots of 8 lanes).  Per
-    // launch of 1024 / 3712 / 14 848 / 65 536 slots: G = 1 -> 0.251 / 0.278 /
-    // 0.314 / 0.317 ms, 2 -> 0.146 / 0.162 / 0.184 / 0.209, 4 -> 0.091 / 0.097 /
-    // 0.110 / 0.207, 8 -> 0.062 / 0.066 / 0.085 / 0.273, 16 -> 0.062 / 0.067 /
-    // 0.140 / 0.507, 32 -> 0.065 / 0.079 / - / 0.978 (MEASUREMENTS.md; the
-    // choice made by reading the code before these numbers was 2)
-    if (p.solver == 6) g = nslots <= 16384 ? 8 : 4;
-    // 2-point SIFT homography solver: 3.3 attempts per slot at 80 % outliers
-    // (3.9 at 95 %: a cubic always has a real root, the failures are the sign
-    // and orientation tests on outlier pairs), each attempt one long serial
-    // chain (the 6 x 9 elimination, the bracket solves), so spare lanes pay
-    // while the waves are resident at once.  Per launch of 1024 / 3712 /
-    // 14 848 / 65 536 slots at 80 % outliers: G = 1 -> 0.466 / 0.520 / 0.571 /
-    // 0.590 ms, 2 -> 0.251 / 0.286 / 0.299 / 0.382, 4 -> 0.142 / 0.152 / 0.162 /
-    // 0.312, 8 -> 0.088 / 0.090 / 0.117 / 0.290, 16 -> 0.052 / 0.056 / 0.109 /
-    // 0.342, 32 -> 0.036 / 0.055 / 0.163 / 0.609 (MEASUREMENTS.md; the choice
-    // made by reading the code before these numbers was the gravity solver's,
-    // 8 up to 16 384 slots and 4 above)
-    if (p.solver == 7) g = nslots <= 2048 ? 32 : nslots <= 16384 ? 16 : 8;
+    int g = gen_lanes(solver, nslots);
     if (env_g == 1 || env_g == 2 || env_g == 4 || env_g == 8 || env_g == 16 || env_g == 32 || env_g == 64) g = env_g;
     switch (g) {
         case 64: go(std::integral_constant<int, 64>{}); break;
@@ -5526,30 +5558,18 @@ __global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t
     for (int j = 0; j < M; ++j) out[(size_t)M * s + j] = ok ? idx[j] : 0xffffffffu;
 }
 
-hipError_t launch_debug_sample(const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
-                               uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
+hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
+                               uint32_t attempt, uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
     if (nslots == 0) return hipSuccess;
-    if (p.solver < 3 || p.solver > 7) return hipErrorInvalidValue;
-    if (guided != nullptr && (guided->n != p.cls[0].n || guided->buckets > kGuidedCoarse || guided->buckets == 0 ||
-                              (size_t)guided->stride * guided->buckets < guided->n))
-        return hipErrorInvalidValue;
+    if (!solver_row(solver).corr) return hipErrorInvalidValue;
+    if (!guided_table_fits(guided, p)) return hipErrorInvalidValue;
     const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
     auto run = [&](auto... t) {
-        if (p.solver == 7)
-            hipLaunchKernelGGL((k_debug_sample<2, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
+        with_corr_solver(solver, [&](auto stag) {
+            constexpr int M = kSolverTable[decltype(stag)::value].m;
+            hipLaunchKernelGGL((k_debug_sample<M, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
                                nslots, attempt, out, t...);
-        else if (p.solver == 6)
-            hipLaunchKernelGGL((k_debug_sample<3, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
-                               nslots, attempt, out, t...);
-        else if (p.solver == 5)
-            hipLaunchKernelGGL((k_debug_sample<5, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
-                               nslots, attempt, out, t...);
-        else if (p.solver == 4)
-            hipLaunchKernelGGL((k_debug_sample<7, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
-                               nslots, attempt, out, t...);
-        else
-            hipLaunchKernelGGL((k_debug_sample<4, decltype(t)...>), grid, block, 0, stream, p.cls[0].n, seed, slot0,
-                               nslots, attempt, out, t...);
+        });
     };
     if (guided != nullptr) run(*guided);
     else run();
@@ -5605,7 +5625,7 @@ hipError_t launch_score_geo(const DevProblem& p, double T, const GeoModel* model
             return true;
         }();
         (void)attr;
-        if (p.solver == 4) {
+        if (p.kind == kKindFundamental) {
             hipLaunchKernelGGL((k_score_fm<4, 16, false>), dim3((nh + 15) / 16), dim3(kSplitThreads), dyn, stream, p,
                                T, 0.0, T * (1.0 + 1e-9), 0.0, FlagBand{}, models, inc, nh, out, ga);
         } else {
@@ -5613,7 +5633,7 @@ hipError_t launch_score_geo(const DevProblem& p, double T, const GeoModel* model
             hipLaunchKernelGGL((k_score_fm<3, 16, false>), dim3((nh + 15) / 16), dim3(kSplitThreads), dyn, stream, p,
                                T, 0.0, sb * sb, 0.0, FlagBand{}, models, inc, nh, out, ga);
         }
-    } else if (p.solver == 4) {
+    } else if (p.kind == kKindFundamental) {
         by_h(std::integral_constant<int, 4>{});
     } else {
         by_h(std::integral_constant<int, 3>{});
@@ -5626,7 +5646,7 @@ hipError_t launch_mask_geo(const DevProblem& p, const GeoModel& model, int rule,
     const DevClass& c = p.cls[0];
     if (c.n == 0) return hipSuccess;
     const dim3 grid(blocks_for(c.n, kMaskBlock)), block(kMaskBlock);
-    if (p.solver == 4)
+    if (p.kind == kKindFundamental)
         hipLaunchKernelGGL(k_mask<4>, grid, block, 0, stream, c, 0, model, rule, T, lambda, 0.0, -1.0, mask);
     else
         hipLaunchKernelGGL(k_mask<3>, grid, block, 0, stream, c, 0, model, rule, T, lambda, 0.0, -1.0, mask);
@@ -5646,7 +5666,7 @@ hipError_t launch_sqres_geo(const DevProblem& p, const GeoModel& model, double* 
     const DevClass& c = p.cls[0];
     if (c.n == 0) return hipSuccess;
     const dim3 grid(blocks_for(c.n, kMaskBlock)), block(kMaskBlock);
-    if (p.solver == 4) hipLaunchKernelGGL(k_sqres<4>, grid, block, 0, stream, c, model, r2);
+    if (p.kind == kKindFundamental) hipLaunchKernelGGL(k_sqres<4>, grid, block, 0, stream, c, model, r2);
     else hipLaunchKernelGGL(k_sqres<3>, grid, block, 0, stream, c, model, r2);
     return hipGetLastError();
 }
@@ -5700,10 +5720,10 @@ __global__ __launch_bounds__(kScoreBlock) void k_inlier_mass(DevClass c, double 
 hipError_t launch_inlier_mass_geo(const DevProblem& p, double T, const GeoModel* models, uint32_t nmodels,
                                   const uint64_t* quanta, uint32_t* count, uint64_t* mass, hipStream_t stream) {
     if (nmodels == 0) return hipSuccess;
-    if (p.solver != 3 && p.solver != 4) return hipErrorInvalidValue;
+    if (p.kind != kKindHomography && p.kind != kKindFundamental) return hipErrorInvalidValue;
     if (models == nullptr || quanta == nullptr || count == nullptr || mass == nullptr) return hipErrorInvalidValue;
     const dim3 grid(nmodels), block(kScoreBlock);
-    if (p.solver == 4) hipLaunchKernelGGL(k_inlier_mass<4>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
+    if (p.kind == kKindFundamental) hipLaunchKernelGGL(k_inlier_mass<4>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
     else hipLaunchKernelGGL(k_inlier_mass<3>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
     return hipGetLastError();
 }
@@ -5712,7 +5732,7 @@ hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc,
                              uint32_t m, double Tm, BatchRecord* out, hipStream_t stream, const uint32_t* hmap,
                              const uint32_t* hcount) {
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(1), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 7 ? kSModels : solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, (uint32_t)solver_row(solver).per, hmap,
                        hcount);
     return hipGetLastError();
 }
@@ -5723,7 +5743,7 @@ hipError_t launch_select_geo_batches(int solver, const ScoreOut& sc, const uint8
     if (count == 0) return hipSuccess;
     if (stride < nh || stride == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_select<GeoModel>, dim3(count), dim3(kSelectThreads), 0, stream, solver, sc, inc,
-                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, solver == 7 ? kSModels : solver == 6 ? kGModels : solver == 5 ? kEModels : solver == 4 ? kFModels : 1u, hmap,
+                       (const GeoModel*)nullptr, nh, slot0, m, 0u, Tm, 0.0, out, (uint32_t)solver_row(solver).per, hmap,
                        hcount, stride);
     return hipGetLastError();
 }

@@ -188,7 +188,7 @@ __global__ __launch_bounds__(64) void k_sum_chain(SumArgs a) {
     coff = wave_sum(coff);
     loff = wave_sum(loff);
     const uint32_t base = k * a.pp, end = min(a.npos, base + a.pp);
-    const int K = a.solver == 2 ? 2 : 1;
+    const int K = solver_classes(a.solver);
     const M* models = static_cast<const M*>(a.models);
     double run = a.bar, pmax = -1.0;
     uint32_t nc = 0, over = 0, nflag = 0;
@@ -205,7 +205,7 @@ __global__ __launch_bounds__(64) void k_sum_chain(SumArgs a) {
             const uint32_t j = a.hmap != nullptr ? hb : p;
             val = finish_at(a.sc, j, K, a.m0, a.m1, a.Tm0, a.Tm1);
             if constexpr (std::is_same<M, RectModel>::value)
-                if (a.solver == 2 && !valid_model_sift22(models[p])) val = -2.0;
+                if (a.solver == GCR_SOLVER_SIFT22 && !valid_model_sift22(models[p])) val = -2.0;
             // flagged decisions: its exact score is the host's to find (a
             // member whatever its twin score, never the running maximum)
             if (val > -2.0 && a.sc.fl != nullptr && a.sc.fl[j] != 0) {
@@ -461,7 +461,7 @@ __global__ __launch_bounds__(64) void k_sum_one(SumArgs a) {
     const int lane = threadIdx.x;
     const uint32_t end = a.npos;
     const bool locate = a.target != ~0ull;
-    const int K = a.solver == 2 ? 2 : 1;
+    const int K = solver_classes(a.solver);
     const M* models = static_cast<const M*>(a.models);
     BlockSummary* out = a.out;
     uint32_t coff = 0, loff = 0, nc = 0, over = 0;
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(64) void k_sum_one(SumArgs a) {
                 const uint32_t j = a.hmap != nullptr ? hb : p;
                 val = finish_at(a.sc, j, K, a.m0, a.m1, a.Tm0, a.Tm1);
                 if constexpr (std::is_same<M, RectModel>::value)
-                    if (a.solver == 2 && !valid_model_sift22(models[p])) val = -2.0;
+                    if (a.solver == GCR_SOLVER_SIFT22 && !valid_model_sift22(models[p])) val = -2.0;
                 // flagged decisions (exact.h): always a member, never the maximum
                 if (val > -2.0 && a.sc.fl != nullptr && a.sc.fl[j] != 0) {
                     flagged = true;
@@ -618,7 +618,7 @@ hipError_t launch_block_summary(int solver, const uint8_t* inc, const void* mode
     a.pcand = reinterpret_cast<PartCand*>(static_cast<char*>(scratch) + (size_t)a.nparts * sizeof(SumPart));
     a.out = out;
     if (a.npos == 0 || a.nparts > (uint32_t)kSumFinalThreads) return hipErrorInvalidValue;
-    const bool rect = solver <= 2;
+    const bool rect = solver_row(solver).rect;
     if (!rect) a.sc.fl = a.sc.lfl = nullptr;   // the correspondence scorers flag nothing (no libm in their residuals)
     // GCR_SUMMARY_ONE=0: one-part summaries through the three launches too
     // (read per launch: tests switch it)
