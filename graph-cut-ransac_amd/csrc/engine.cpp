@@ -340,6 +340,9 @@ struct Workspace {
     // (guided_stop.h; uint64_t bit patterns), which a run's mass launches read
     // on the replay stream -- the same lifetime rule.
     DevBuf<double> guided_tab;
+    // PROSAC sampling: the problem's growth table (prosac.h, N + 1 entries),
+    // under the same lifetime rule
+    DevBuf<uint64_t> prosac_tab;
     // the guided stop's mass launches (RunnerT::inlier_masses): the models in
     // pinned memory and on the device, each model's (count, mass) pinned
     PinBuf<GeoModel> gm_hmodels;
@@ -600,6 +603,11 @@ struct gcr_problem {
         const char* e = getenv("GCR_GUIDED_FLAT");
         return (e && e[0] == '1') ? &gt_flat : &gt;
     }
+    // PROSAC sampling (prosac.h, gcr_problem_set_prosac): the growth table in
+    // the workspace's prosac_tab; pt.g == nullptr: not set.  Exclusive with
+    // gt.  Handed to the generator launches only.
+    ProsacTable pt{};
+    const ProsacTable* prosac() const { return pt.g ? &pt : nullptr; }
     // Calibrated solvers: hc[0] and the device SoA hold the K-normalised
     // correspondences.  Host only: the pixel columns (the neighbourhood
     // grid is built over them) and the divisor that takes a pixel threshold
@@ -1762,7 +1770,8 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static bool valid(int, const Model&) { return true; }
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
-        return launch_generate_geo(P->solver, P->dp, seed, s0, n, inc, m, s, P->guided(), P->grav(), P->sift());
+        return launch_generate_geo(P->solver, P->dp, seed, s0, n, inc, m, s, P->guided(), P->grav(), P->sift(),
+                                   P->prosac());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1822,7 +1831,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
         hipError_t e = launch_generate_geo(P->solver, P->dp, seed, s0, n, b.inc, b.models, s, P->guided(), P->grav(),
-                                           P->sift());
+                                           P->sift(), P->prosac());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -4444,6 +4453,9 @@ int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling exists for homography, "
                                    "SIFT homography, fundamental- and essential-matrix (5-point, gravity) "
                                    "problems only");
+    if (prob->pt.g != nullptr)
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem samples with PROSAC "
+                                   "(gcr_problem_set_prosac), whose stop is the uniform bound");
     if (prob->gt.cdf == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
                                    "(gcr_problem_set_probabilities)");
@@ -4469,6 +4481,9 @@ int check_sift_rows(const gcr_problem* prob) {
 int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
     if (!is_corr(prob->solver))
         return set_err(GCR_EINVAL, "guided sampling: homography and fundamental-matrix problems only");
+    if (w != nullptr && prob->pt.g != nullptr)
+        return set_err(GCR_EINVAL, "probabilities: the problem samples with PROSAC; clear it first "
+                                   "(gcr_problem_set_prosac(prob, 0))");
     std::vector<double> tab;
     GuidedTable t{};
     if (w != nullptr) {
@@ -4506,6 +4521,44 @@ int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
         static_assert(sizeof(uint64_t) == sizeof(double), "quanta share guided_tab");
         prob->gq = reinterpret_cast<const uint64_t*>(prob->w->guided_tab.p + ntab);
         prob->gQ = Q;
+        return GCR_OK;
+    });
+}
+
+// gcr_problem_set_prosac: set_probabilities' order of things with prosac.h's
+// growth table.  Every check comes before the first change, so a refused call
+// leaves the problem as it was.
+int set_prosac(gcr_problem* prob, uint64_t convergence) {
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "PROSAC sampling: correspondence problems only (homography, SIFT homography, "
+                                   "fundamental and essential matrix)");
+    const size_t n = prob->hc[0].n, m = minimal_size(prob->solver);
+    std::vector<uint64_t> g;
+    if (convergence != 0) {
+        if (convergence > kProsacMaxConvergence)
+            return set_err(GCR_EINVAL, "PROSAC sampling: convergence_iterations %llu is above 2^40",
+                           (unsigned long long)convergence);
+        if (prob->gt.cdf != nullptr)
+            return set_err(GCR_EINVAL, "PROSAC sampling: the problem has probabilities set (guided sampling); "
+                                       "clear them first (gcr_problem_set_probabilities(prob, NULL, 0))");
+        if (n < m || n >= 0xffffffffull)
+            return set_err(GCR_EINVAL, "PROSAC sampling: %zu correspondences, a minimal sample takes %zu", n, m);
+        g.resize(n + 1);
+        prosac_growth((uint32_t)n, (uint32_t)m, convergence, g.data());
+    }
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        HIPC(hipStreamSynchronize(prob->ctx->side));
+        HIPC(hipStreamSynchronize(prob->ctx->stream));
+        prob->pt = ProsacTable{};
+        if (convergence == 0) return GCR_OK;
+        prob->w->prosac_tab.ensure(g.size());
+        HIPC(hipMemcpy(prob->w->prosac_tab.p, g.data(), g.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        prob->pt.g = prob->w->prosac_tab.p;
+        prob->pt.n = (uint32_t)n;
+        prob->pt.m = (uint32_t)m;
+        prob->pt.g_n = g[n];
         return GCR_OK;
     });
 }
@@ -4696,6 +4749,11 @@ void gcr_problem_destroy(gcr_problem* prob) {
 int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities, size_t n) {
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     return set_probabilities(prob, probabilities, n);
+}
+
+int gcr_problem_set_prosac(gcr_problem* prob, uint64_t convergence_iterations) {
+    if (!prob) return set_err(GCR_EINVAL, "null problem");
+    return set_prosac(prob, convergence_iterations);
 }
 
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
@@ -5225,7 +5283,7 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
         HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s,
-                                 prob->guided(), prob->grav(), prob->sift()));
+                                 prob->guided(), prob->grav(), prob->sift(), prob->prosac()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -5245,7 +5303,8 @@ int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_
         DevBuf<uint32_t> out;
         out.ensure(std::max<size_t>(cnt, 1));
         hipStream_t s = prob->ctx->stream;
-        HIPC(launch_debug_sample(prob->solver, prob->dp, seed, slot0, nslots, attempt, out.p, s, prob->guided()));
+        HIPC(launch_debug_sample(prob->solver, prob->dp, seed, slot0, nslots, attempt, out.p, s, prob->guided(),
+                                 prob->prosac()));
         HIPC(hipMemcpyAsync(idx_out, out.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
         return GCR_OK;
@@ -5266,11 +5325,12 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
         hipStream_t s = prob->ctx->stream;
         // one untimed launch first (code object load, caches)
         HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s,
-                                 prob->guided(), prob->grav(), prob->sift()));
+                                 prob->guided(), prob->grav(), prob->sift(), prob->prosac()));
         HIPC(hipEventRecord(prob->ctx->ev0, s));
         for (int r = 0; r < reps; ++r)
             HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
-                                     prob->w->gmodels.p, s, prob->guided(), prob->grav(), prob->sift()));
+                                     prob->w->gmodels.p, s, prob->guided(), prob->grav(), prob->sift(),
+                                     prob->prosac()));
         HIPC(hipEventRecord(prob->ctx->ev1, s));
         HIPC(hipEventSynchronize(prob->ctx->ev1));
         float ms = 0.f;
@@ -5678,6 +5738,44 @@ int gcr_host_sample(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream
     if (!out || m > 32) return set_err(GCR_EINVAL, "bad sample request");
     WordStream ws(seed, index, sub, stream, cls);
     return sample_distinct<32>(ws, n, (int)m, out) ? GCR_OK : set_err(GCR_EINTERNAL, "sample budget exhausted");
+}
+
+static int check_prosac_args(size_t n, uint32_t m, uint64_t convergence) {
+    if (m == 0 || m > 32 || n < m || n >= 0xffffffffull || convergence == 0 || convergence > kProsacMaxConvergence)
+        return set_err(GCR_EINVAL, "PROSAC: need 1 <= m <= 32, m <= n < 2^32 - 1 and 1 <= convergence <= 2^40");
+    return GCR_OK;
+}
+
+int gcr_host_prosac_growth(size_t n, uint32_t m, uint64_t convergence, uint64_t* g_out) {
+    if (!g_out) return set_err(GCR_EINVAL, "null output pointer");
+    if (int e = check_prosac_args(n, m, convergence)) return e;
+    prosac_growth((uint32_t)n, m, convergence, g_out);
+    return GCR_OK;
+}
+
+int gcr_host_prosac_pool(size_t n, uint32_t m, uint64_t convergence, uint64_t slot, uint32_t* pool_out) {
+    if (!pool_out) return set_err(GCR_EINVAL, "null output pointer");
+    if (int e = check_prosac_args(n, m, convergence)) return e;
+    return guard([&]() -> int {
+        std::vector<uint64_t> g(n + 1);
+        prosac_growth((uint32_t)n, m, convergence, g.data());
+        *pool_out = prosac_pool_flat(g.data(), (uint32_t)n, m, slot);
+        return GCR_OK;
+    });
+}
+
+int gcr_host_sample_prosac(uint64_t seed, uint64_t index, uint32_t sub, size_t n, uint32_t m, uint64_t convergence,
+                           uint32_t* out) {
+    if (!out) return set_err(GCR_EINVAL, "null output pointer");
+    if (int e = check_prosac_args(n, m, convergence)) return e;
+    return guard([&]() -> int {
+        std::vector<uint64_t> g(n + 1);
+        prosac_growth((uint32_t)n, m, convergence, g.data());
+        WordStream ws(seed, index, sub, kStreamMain, 0);
+        const uint32_t pool = prosac_pool_flat(g.data(), (uint32_t)n, m, prosac_slot(ws));
+        return sample_prosac<32>(ws, n, (int)m, pool, out) ? GCR_OK
+                                                           : set_err(GCR_EINTERNAL, "sample budget exhausted");
+    });
 }
 
 int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m) {

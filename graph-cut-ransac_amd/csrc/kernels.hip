@@ -19,6 +19,7 @@
 #include "grav.h"
 #include "guided.h"
 #include "philox.h"
+#include "prosac.h"
 #include "qr3.h"
 #include "sifth.h"
 
@@ -40,32 +41,69 @@ constexpr int kMaskBlock = 256;
 
 // ------------------------------------------------------------- generate ----
 // How the correspondence estimators' attempts draw their sample: uniformly
-// (philox.h sample_distinct) or guided by the problem's probabilities
-// (guided.h), the coarse table read from the workgroup's LDS copy.
+// (philox.h sample_distinct), guided by the problem's probabilities
+// (guided.h), the coarse table read from the workgroup's LDS copy, or by
+// PROSAC's growing pool (prosac.h), the slot's pool size searched in the
+// workgroup's LDS window of the growth table.
 struct UniformDraw {};
 struct GuidedDraw {
     GuidedTable t;
     const double* coarse;               // LDS (stage_draw)
 };
+struct ProsacDraw {
+    const uint64_t* win;                // LDS (stage_draw): g[n_lo .. n_lo + kProsacWindow), all-ones past N
+    uint32_t n_lo;
+    uint32_t n;                         // N
+    uint64_t g_n;                       // g[N]
+};
 
 template <int M, class DRAW>
 GCR_DEVICE bool draw_sample(WordStream& ws, uint64_t n, const DRAW& d, uint32_t* idx) {
-    if constexpr (std::is_same_v<DRAW, GuidedDraw>) return sample_guided<M>(ws, d.t, d.coarse, M, idx);
-    else return sample_distinct<M>(ws, n, M, idx);
+    if constexpr (std::is_same_v<DRAW, GuidedDraw>) {
+        return sample_guided<M>(ws, d.t, d.coarse, M, idx);
+    } else if constexpr (std::is_same_v<DRAW, ProsacDraw>) {
+        const uint64_t slot = prosac_slot(ws);
+        uint32_t pool = 0;
+        if (slot < d.g_n) {
+            const uint32_t i = prosac_first(d.win, 0u, kProsacWindow, slot);
+            pool = i < d.n - d.n_lo ? d.n_lo + i : d.n;     // (a slot of this workgroup never needs the clamp)
+        }
+        return sample_prosac<M>(ws, d.n, M, pool, idx);
+    } else {
+        return sample_distinct<M>(ws, n, M, idx);
+    }
 }
 
 // A generator kernel's trailing arguments are nothing (uniform draws: the
-// kernel is the one it was without guided sampling) or one GuidedTable.  Then
-// the workgroup copies the coarse table to LDS once; every thread of the
-// workgroup calls this before anything else, so all waves reach the barrier
-// (the widening generator's lanes change slots between rounds: the copy
-// belongs to the workgroup, not to a slot).
+// kernel is the one it was without guided sampling), one GuidedTable or one
+// ProsacTable.  Then the workgroup copies the coarse table (the growth
+// table's window of its slots) to LDS once; every thread of the workgroup
+// calls this before anything else, so all waves reach the barrier (the
+// widening generator's lanes change slots between rounds: the copy belongs to
+// the workgroup, not to a slot).
 GCR_DEVICE UniformDraw stage_draw() { return UniformDraw{}; }
 GCR_DEVICE GuidedDraw stage_draw(const GuidedTable& t) {
     __shared__ double s_coarse[kGuidedCoarse];
     for (uint32_t i = threadIdx.x; i < t.buckets && i < kGuidedCoarse; i += blockDim.x) s_coarse[i] = t.coarse[i];
     __syncthreads();
     return GuidedDraw{t, s_coarse};
+}
+// A workgroup of kGenBlock threads covers at most kGenBlock consecutive slots
+// from slot0 + blockIdx.x * kGenBlock / lanes, in every generator: n_lo by one
+// search through global memory (every thread the same, uniform addresses),
+// then the window (prosac.h).  A workgroup that starts past g[N] needs none.
+GCR_DEVICE ProsacDraw stage_draw(const ProsacTable& t) {
+    static_assert(kProsacWindow == kGenBlock, "one window entry per slot a workgroup can cover");
+    __shared__ uint64_t s_win[kProsacWindow];
+    const uint64_t first = t.slot0 + (uint64_t)(blockIdx.x * (uint32_t)kGenBlock) / t.lanes;
+    uint32_t n_lo = t.n;
+    if (first < t.g_n) {
+        n_lo = prosac_first(t.g, t.m, t.n, first);
+        for (uint32_t i = threadIdx.x; i < kProsacWindow; i += blockDim.x)
+            s_win[i] = i <= t.n - n_lo ? t.g[n_lo + i] : ~0ull;
+    }
+    __syncthreads();
+    return ProsacDraw{s_win, n_lo, t.n, t.g_n};
 }
 
 // One attempt of one outer-iteration slot: Philox sample -> sample validity ->
@@ -5425,6 +5463,12 @@ bool with_corr_solver(int solver, F&& f) {
     }
 }
 
+// the PROSAC table of this problem and solver, never together with a guided one
+bool prosac_table_fits(const ProsacTable* prosac, const GuidedTable* guided, const DevProblem& p, int m) {
+    return prosac == nullptr || (guided == nullptr && prosac->g != nullptr && prosac->n == p.cls[0].n &&
+                                 prosac->m == (uint32_t)m && prosac->n >= prosac->m && prosac->g_n >= 1);
+}
+
 bool guided_table_fits(const GuidedTable* guided, const DevProblem& p) {
     return guided == nullptr || (guided->n == p.cls[0].n && guided->buckets <= kGuidedCoarse && guided->buckets != 0 &&
                                  (size_t)guided->stride * guided->buckets >= guided->n);
@@ -5475,13 +5519,15 @@ int gen_lanes(int solver, uint32_t nslots) {
 
 hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
                                uint8_t* inc, GeoModel* models, hipStream_t stream, const GuidedTable* guided,
-                               const GravRot* grav, const SiftCols* sift) {
+                               const GravRot* grav, const SiftCols* sift, const ProsacTable* prosac) {
     if (nslots == 0) return hipSuccess;
     const SolverRow row = solver_row(solver);
     if (!row.corr || row.kind != p.kind) return hipErrorInvalidValue;
     if (row.needs_gravity != (grav != nullptr)) return hipErrorInvalidValue;
     if (row.needs_sift != (sift != nullptr)) return hipErrorInvalidValue;
-    if (!guided_table_fits(guided, p)) return hipErrorInvalidValue;
+    if (!guided_table_fits(guided, p) || !prosac_table_fits(prosac, guided, p, row.m)) return hipErrorInvalidValue;
+    // a launch that starts past g[N] is the uniform kernel itself, no table
+    if (prosac != nullptr && slot0 >= prosac->g_n) prosac = nullptr;
     // GCR_GEN_WIDEN=0: the fundamental-matrix generator keeps fixed groups of
     // G lanes per slot (k_generate_f) instead of widening them (k_generate_fw).
     // Both knobs are read per launch (tests switch them in-process).
@@ -5493,7 +5539,7 @@ hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, u
     auto go = [&](auto gtag) {
         constexpr int G = decltype(gtag)::value;
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
-        // t: nothing (the uniform kernels) or the guided table
+        // t: nothing (the uniform kernels), the guided table or the PROSAC table
         auto run = [&](auto... t) {
             with_corr_solver(solver, [&](auto stag) {
                 constexpr int S = decltype(stag)::value;
@@ -5522,8 +5568,16 @@ hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, u
                 }
             });
         };
-        if (guided != nullptr) run(*guided);
-        else run();
+        if (guided != nullptr) {
+            run(*guided);
+        } else if (prosac != nullptr) {
+            ProsacTable pt = *prosac;
+            pt.slot0 = slot0;
+            pt.lanes = (uint32_t)G;
+            run(pt);
+        } else {
+            run();
+        }
     };
     // GCR_GEN_G overrides the lanes per slot (1 .. 64)
     const char* eg = getenv("GCR_GEN_G");
@@ -5559,10 +5613,13 @@ __global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t
 }
 
 hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
-                               uint32_t attempt, uint32_t* out, hipStream_t stream, const GuidedTable* guided) {
+                               uint32_t attempt, uint32_t* out, hipStream_t stream, const GuidedTable* guided,
+                               const ProsacTable* prosac) {
     if (nslots == 0) return hipSuccess;
     if (!solver_row(solver).corr) return hipErrorInvalidValue;
-    if (!guided_table_fits(guided, p)) return hipErrorInvalidValue;
+    if (!guided_table_fits(guided, p) || !prosac_table_fits(prosac, guided, p, solver_row(solver).m))
+        return hipErrorInvalidValue;
+    if (prosac != nullptr && slot0 >= prosac->g_n) prosac = nullptr;
     const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
     auto run = [&](auto... t) {
         with_corr_solver(solver, [&](auto stag) {
@@ -5571,8 +5628,16 @@ hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, u
                                nslots, attempt, out, t...);
         });
     };
-    if (guided != nullptr) run(*guided);
-    else run();
+    if (guided != nullptr) {
+        run(*guided);
+    } else if (prosac != nullptr) {
+        ProsacTable pt = *prosac;
+        pt.slot0 = slot0;
+        pt.lanes = 1;
+        run(pt);
+    } else {
+        run();
+    }
     return hipGetLastError();
 }
 

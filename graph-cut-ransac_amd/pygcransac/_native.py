@@ -216,6 +216,12 @@ def _load():
     L.gcr_host_guided_quanta.argtypes = [vp, C.c_size_t, C.c_uint32, u64p, u64p]
     L.gcr_host_guided_iterations.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_double, u64p]
     L.gcr_debug_inlier_mass_h.argtypes = [vp, C.POINTER(Params), dp, C.c_uint32, u32p, u64p]
+    # PROSAC sampling (csrc/prosac.h): gcr_problem_set_prosac and its host definition
+    L.gcr_problem_set_prosac.argtypes = [vp, C.c_uint64]
+    L.gcr_host_prosac_growth.argtypes = [C.c_size_t, C.c_uint32, C.c_uint64, u64p]
+    L.gcr_host_prosac_pool.argtypes = [C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
+    L.gcr_host_sample_prosac.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint64,
+                                         u32p]
     # essential matrix (csrc/ess.h): pixel rows + calibration matrices
     L.gcr_find_essential_matrix.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Params), vp, vp,
                                             C.POINTER(Stats)]

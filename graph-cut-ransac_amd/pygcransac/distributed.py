@@ -235,7 +235,8 @@ class Comm:
 
 def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None, rank: int = 0, world: int = 1,
                         dist=None, device: Optional[int] = None, coll_device=None, comm: Optional[Comm] = None,
-                        probabilities=None, K1=None, K2=None, G1=None, G2=None, sift=None):
+                        probabilities=None, K1=None, K2=None, G1=None, G2=None, sift=None,
+                        prosac_convergence: Optional[int] = None):
     """One estimator problem over `world` ranks.
 
     Every rank calls this with the same inputs; each verifies its block of
@@ -250,6 +251,12 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     ``params={"flags": _native.FLAG_GUIDED_STOP, ...}`` stops the run on the
     inlier mass (every rank computes the chain members' masses itself: the
     exchanged records are the same).
+    `prosac_convergence` (correspondence solvers; exclusive with
+    `probabilities`) switches the problem to PROSAC sampling
+    (gcr_problem_set_prosac, csrc/prosac.h) with that convergence length, the
+    same on every rank: the rows are expected in quality order, best first, as
+    in the C ABI.  A slot's pool is a function of the slot index alone, so the
+    sharded run stays bit-identical to the single-rank one.
     Solver 5 (essential matrix) takes pixel rows and the calibration matrices
     `K1`, `K2` (3 x 3); its threshold is in pixels and H is E in normalised
     coordinates.  Solver 6 (essential matrix with known gravity) takes the
@@ -295,6 +302,8 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
         if probabilities is not None:
             w = np.ascontiguousarray(probabilities, dtype=np.float64).reshape(-1)
             N.check(N.lib.gcr_problem_set_probabilities(h, w.ctypes.data, w.shape[0]))
+        if prosac_convergence is not None:
+            N.check(N.lib.gcr_problem_set_prosac(h, int(prosac_convergence)))
         p = N.default_params()
         for k, v in (params or {}).items():
             setattr(p, k, v)

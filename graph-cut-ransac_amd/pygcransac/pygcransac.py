@@ -443,21 +443,59 @@ def _as_probabilities(probabilities, n, m):
     return w
 
 
+PROSAC_MAX_CONVERGENCE = 1 << 40
+
+
+def _as_scores(scores, n):
+    """PROSAC's quality scores as a float64 vector of length n: one per
+    correspondence, higher is better, every value finite."""
+    q = np.asarray(scores, dtype=np.float64)
+    if q.ndim != 1 or q.shape[0] != n:
+        raise ValueError(f"probabilities must be a vector with one quality score per correspondence ({n}); "
+                         f"it has shape {tuple(q.shape)}.")
+    if not np.all(np.isfinite(q)):
+        raise ValueError("sampler=1 (PROSAC) orders the correspondences by their scores: every score must be finite.")
+    if n > 1 and q.min() == q.max():
+        # ties keep the input order, but scores that are ALL equal rank nothing: the run would sample the first
+        # rows first for no reason the caller gave (all-ones weights, sampler 3's neutral vector, end up here)
+        raise ValueError(f"sampler=1 (PROSAC) needs scores that rank the correspondences: all {n} are equal. "
+                         f"Uniform sampling is sampler=0; rows already in quality order take -np.arange(n).")
+    return q
+
+
+def prosac_order(scores):
+    """The row order PROSAC samples in: by score descending, ties in input
+    order (a stable sort)."""
+    return np.argsort(-np.asarray(scores, dtype=np.float64), kind="stable")
+
+
+def _as_convergence(prosac_convergence):
+    t = _as_size_t(prosac_convergence, "prosac_convergence")
+    if t < 1 or t > PROSAC_MAX_CONVERGENCE:
+        raise ValueError(f"prosac_convergence must be in 1 .. 2^40, got {prosac_convergence}.")
+    return t
+
+
 def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                          spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
-                         batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False, min_weights=None):
+                         batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False, min_weights=None,
+                         create=None, prosac_convergence=100000):
     """min_weights: the minimal sample size the probabilities are checked for
-    (default: min_rows)."""
+    (default: min_rows).  create(ctx, rows, order, out): a resident problem of
+    the estimator over `rows`, the caller's rows taken in `order` (sampler=1)."""
     for name, v in (("h1", h1), ("w1", w1), ("h2", h2), ("w2", w2)):
         _as_double(v, name)
     sampler_id = _as_size_t(sampler, "sampler")
-    if sampler_id not in (0, 3):
-        raise ValueError(f"Unsupported sampler {sampler}: only 0 (uniform) and 3 (guided by probabilities, "
-                         f"importance sampling) are supported.")
+    if sampler_id not in (0, 1, 3):
+        raise ValueError(f"Unsupported sampler {sampler}: only 0 (uniform), 1 (PROSAC, ordered by quality scores) "
+                         f"and 3 (guided by probabilities, importance sampling) are supported.")
     if sampler_id == 0 and probabilities is not None and len(probabilities) != 0:
         raise ValueError("The uniform sampler (0) takes no probabilities; they must be empty (sampler=3 uses them).")
     if sampler_id == 3 and probabilities is None:
         raise ValueError("sampler=3 (guided) needs probabilities, one per correspondence.")
+    if sampler_id == 1 and probabilities is None:
+        raise ValueError("sampler=1 (PROSAC) needs probabilities: one quality score per correspondence, higher is "
+                         "better (rows already in quality order: -np.arange(n)).")
     if guided_stop and sampler_id != 3:
         raise ValueError("guided_stop=True stops on the guided sampler's inlier mass: it needs sampler=3 "
                          "with probabilities.")
@@ -477,8 +515,25 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     M = np.zeros(9, dtype=np.float64)
     st = N.Stats()
     w = _as_probabilities(probabilities, n, min_weights or min_rows) if sampler_id == 3 else None
+    if sampler_id == 1:
+        convergence = _as_convergence(prosac_convergence)
+        order = prosac_order(_as_scores(probabilities, n))
     ctx = N.context(device)
-    if sampler_id == 3:
+    if sampler_id == 1:
+        # the resident-problem API on the rows in quality order; the mask goes
+        # back to the caller's order
+        rows = np.ascontiguousarray(f[order])
+        h = C.c_void_p()
+        N.check(create(ctx, rows, order, C.byref(h)))
+        try:
+            N.check(N.lib.gcr_problem_set_prosac(h, convergence))
+            ordered = np.zeros(n, dtype=np.uint8)
+            rc = N.lib.gcr_problem_run(h, C.byref(p), ordered.ctypes.data_as(C.POINTER(C.c_uint8)), None,
+                                       M.ctypes.data_as(C.POINTER(C.c_double)), C.byref(N.RectModel()), C.byref(st))
+        finally:
+            N.lib.gcr_problem_destroy(h)
+        mask[order] = ordered
+    elif sampler_id == 3:
         rc = guided_entry(ctx, f.ctypes.data, n, w.ctypes.data, C.byref(p), mask.ctypes.data, M.ctypes.data,
                           C.byref(st))
     else:
@@ -491,9 +546,17 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     return (M.reshape(3, 3), inliers) + extra
 
 
+def _plain_create(solver):
+    def create(ctx, rows, order, out):
+        return N.lib.gcr_problem_create(ctx, solver, rows.ctypes.data_as(C.POINTER(C.c_double)), rows.shape[0], None,
+                                        0, out)
+    return create
+
+
 def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                    spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
-                   neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False, guided_stop=False):
+                   neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False, guided_stop=False,
+                   prosac_convergence=100000):
     """4-point homography with graph-cut LO -- an EXTENSION (SURVEY.md §8(f)
     row 3): this fork has no homography estimator (finding 0.1); the argument
     names and order follow upstream pygcransac's findHomography.
@@ -516,7 +579,19 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     weights (csrc/guided_stop.h), so a run with informative weights returns as
     soon as its own sampler justifies it.  With all-equal weights both stops
     are identical.  The bound is meaningful when no single weight dominates
-    the sum.  ``threshold`` is the inlier threshold in pixels
+    the sum.  ``sampler=1`` is PROSAC (upstream's sampler 1; csrc/prosac.h is
+    the definition): ``probabilities`` then holds one quality score per
+    correspondence, higher is better, every value finite (a SIFT ratio-test
+    value negated, a descriptor similarity; rows already in quality order:
+    ``-np.arange(n)``; scores that are all equal rank nothing and are a
+    ValueError).  The rows are sorted by score descending (stable: ties
+    keep their order), early iterations sample among the best-ranked rows, the
+    pool grows on PROSAC's schedule of ``prosac_convergence`` iterations
+    (1 .. 2^40) and past it every iteration is the uniform sampler's; the mask
+    comes back in the caller's order.  Only an order is needed, and the stop
+    stays the reference's uniform bound (PROSAC's own non-randomness /
+    maximality stop is not implemented); ``guided_stop`` does not apply.
+    ``threshold`` is the inlier threshold in pixels
     of the second image (MSAC threshold 2.25 * threshold, as the rectification
     solvers).
 
@@ -525,19 +600,22 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     return _correspondence_call(N.lib.gcr_find_homography, N.lib.gcr_find_homography_guided, correspondences,
                                 h1, w1, h2, w2, probabilities, threshold, conf, spatial_coherence_weight, max_iters,
                                 min_iters, sampler, lo_number,
-                                seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop)
+                                seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
+                                create=_plain_create(N.SOLVER_HOMOGRAPHY4), prosac_convergence=prosac_convergence)
 
 
 def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                           spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50,
                           *, neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                          guided_stop=False):
+                          guided_stop=False, prosac_convergence=100000):
     """7-point fundamental matrix with graph-cut LO -- an EXTENSION like
     findHomography (same arguments, the same neighbourhood grid; upstream
     pygcransac's findFundamentalMatrix order).  The residual is the Sampson distance in pixels; a sample yields up
     to three models, each scored.  ``sampler=3`` with ``probabilities`` (at least
     7 of them > 0) guides the 7-point samples as it does findHomography's, and
-    ``guided_stop=True`` stops such a run on the inlier mass, as there.
+    ``guided_stop=True`` stops such a run on the inlier mass, as there;
+    ``sampler=1`` with quality scores and ``prosac_convergence`` is PROSAC, as
+    there.
 
     Returns ``(F, inliers)`` with F (3, 3), unit Frobenius norm and
     x2^T F x1 = 0, or ``(None, inliers)``.
@@ -545,7 +623,8 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
     return _correspondence_call(N.lib.gcr_find_fundamental_matrix, N.lib.gcr_find_fundamental_matrix_guided,
                                 correspondences, h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
-                                seed, device, batch_slots, return_stats, 7, neighborhood_size, guided_stop)
+                                seed, device, batch_slots, return_stats, 7, neighborhood_size, guided_stop,
+                                create=_plain_create(N.SOLVER_FUNDAMENTAL7), prosac_convergence=prosac_convergence)
 
 
 def _as_calibration(K, name):
@@ -558,7 +637,7 @@ def _as_calibration(K, name):
 def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                         spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                         neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                        guided_stop=False):
+                        guided_stop=False, prosac_convergence=100000):
     """5-point essential matrix with graph-cut LO for calibrated cameras -- an
     EXTENSION like findFundamentalMatrix (upstream pygcransac's
     findEssentialMatrix order; csrc/ess.h is the solver's definition).
@@ -570,7 +649,8 @@ def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=N
     by the mean of the four focal lengths (upstream's rule).  The neighbourhood
     grid lies over the pixel coordinates, as findFundamentalMatrix's.  A sample
     yields up to ten models, each scored.  ``sampler``, ``probabilities`` (at
-    least 5 of them > 0) and ``guided_stop`` as in findHomography.
+    least 5 of them > 0) and ``guided_stop`` as in findHomography, and so are
+    ``sampler=1`` (PROSAC: quality scores) and ``prosac_convergence``.
 
     Returns ``(E, inliers)`` with E (3, 3), unit Frobenius norm and
     (K2^-1 x2)^T E (K1^-1 x1) = 0, or ``(None, inliers)``.
@@ -586,9 +666,14 @@ def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=N
     def guided_entry(ctx, f, n, w, p, mask, M, st):
         return N.lib.gcr_find_essential_matrix(ctx, f, n, k1.ctypes.data, k2.ctypes.data, w, p, mask, M, st)
 
+    def create(ctx, rows, order, out):
+        return N.lib.gcr_problem_create_essential(ctx, rows.ctypes.data, rows.shape[0], k1.ctypes.data,
+                                                  k2.ctypes.data, out)
+
     return _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
-                                batch_slots, return_stats, 5, neighborhood_size, guided_stop)
+                                batch_slots, return_stats, 5, neighborhood_size, guided_stop, create=create,
+                                prosac_convergence=prosac_convergence)
 
 
 def _as_rotation(G, name):
@@ -601,7 +686,8 @@ def _as_rotation(G, name):
 def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_destination, h1, w1, h2, w2,
                                probabilities=None, threshold=1.0, conf=0.99, spatial_coherence_weight=0.975,
                                max_iters=10000, min_iters=50, sampler=0, lo_number=50, *, neighborhood_size=8, seed=0,
-                               device=None, batch_slots=0, return_stats=False, guided_stop=False):
+                               device=None, batch_slots=0, return_stats=False, guided_stop=False,
+                               prosac_convergence=100000):
     """3-point essential matrix with graph-cut LO for calibrated cameras whose
     gravity direction is known (a phone, a vehicle, any IMU rig) -- an
     EXTENSION like findEssentialMatrix (upstream pygcransac's
@@ -616,7 +702,8 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
     correspondences and yields up to four models; at 80 % outliers the stop
     needs about 570 iterations where the 5-point solver needs about 14 400.
     A half turn about the vertical between the aligned frames is outside the
-    solver's parametrisation.  ``probabilities`` need at least 3 weights > 0.
+    solver's parametrisation.  ``probabilities`` need at least 3 weights > 0
+    (``sampler=3``; with ``sampler=1``, PROSAC, they are quality scores).
 
     Returns ``(E, inliers)`` with E (3, 3) in the ordinary K-normalised frames,
     findEssentialMatrix's convention: unit Frobenius norm and
@@ -638,15 +725,20 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
         return N.lib.gcr_find_gravity_essential_matrix(ctx, f, n, k1.ctypes.data, k2.ctypes.data, g1.ctypes.data,
                                                        g2.ctypes.data, w, p, mask, M, st)
 
+    def create(ctx, rows, order, out):
+        return N.lib.gcr_problem_create_gravity_essential(ctx, rows.ctypes.data, rows.shape[0], k1.ctypes.data,
+                                                          k2.ctypes.data, g1.ctypes.data, g2.ctypes.data, out)
+
     return _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
-                                batch_slots, return_stats, 3, neighborhood_size, guided_stop)
+                                batch_slots, return_stats, 3, neighborhood_size, guided_stop, create=create,
+                                prosac_convergence=prosac_convergence)
 
 
 def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                        spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                        neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                       guided_stop=False):
+                       guided_stop=False, prosac_convergence=100000):
     """Homography from TWO SIFT correspondences with graph-cut LO -- an
     EXTENSION like findHomography (what upstream pygcransac's findHomography
     runs with its SIFT-based solver).  Upstream's solver is not part of this
@@ -664,7 +756,8 @@ def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, thre
     optimisation; scoring, the threshold, LO's fits (the 4-point estimator's
     non-minimal fit), the neighbourhood grid and every other argument are
     findHomography's.  ``probabilities`` (``sampler=3``) need at least 2 weights
-    > 0.
+    > 0.  With ``sampler=1`` (PROSAC, as in findHomography) they are quality
+    scores; the SIFT columns are sorted with their rows.
 
     Returns ``(H, inliers)`` with H (3, 3) and H[2, 2] = 1, or ``(None, inliers)``.
     """
@@ -685,7 +778,11 @@ def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, thre
     def guided_entry(ctx, f, n, w, p, mask, M, st):
         return N.lib.gcr_find_homography_sift(ctx, f, sift.ctypes.data, n, w, p, mask, M, st)
 
+    def create(ctx, rows, order, out):
+        cols = np.ascontiguousarray(sift[order])
+        return N.lib.gcr_problem_create_sift_homography(ctx, rows.ctypes.data, cols.ctypes.data, rows.shape[0], out)
+
     return _correspondence_call(entry, guided_entry, np.ascontiguousarray(f8[:, :4]), h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
-                                min_weights=2)
+                                min_weights=2, create=create, prosac_convergence=prosac_convergence)

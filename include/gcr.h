@@ -332,6 +332,26 @@ void gcr_problem_destroy(gcr_problem* prob);
  * previous run left in flight.  Rectification problems: GCR_EINVAL.
  * gcr_solve_batch's items carry no probabilities and stay uniform. */
 int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities, size_t n);
+/* PROSAC sampling (upstream's sampler 1; csrc/prosac.h is the definition)
+ * for a resident correspondence problem -- every solver the guided sampler is
+ * valid for.  The problem's rows must be in quality order, best first.  Early
+ * slots draw from the best-ranked rows, the pool grows on a fixed schedule of
+ * `convergence_iterations` (T_N; 1 .. 2^40, upstream's default is 100000) and
+ * past it every slot draws the uniform sampler's own sample.  The pool is a
+ * function of the slot index alone, so runs stay bit-identical across
+ * batch_slots, shards and ranks.  Everything that generates from the problem
+ * afterwards -- gcr_problem_run, _run_sharded, _run_comm, _verify_batch(es),
+ * gcr_debug_generate_h, gcr_debug_sample_h, gcr_measure_generate_h -- uses
+ * it; local optimisation's inner sampler stays uniform and the stop is the
+ * uniform bound (PROSAC's own non-randomness / maximality stop is not
+ * implemented).  convergence_iterations == 0 returns the problem to uniform
+ * sampling.  Either call first waits for a speculative chunk a previous run
+ * left in flight.  GCR_EINVAL, the problem left as it was: rectification
+ * problems, convergence_iterations > 2^40, a problem with probabilities set
+ * (guided and PROSAC sampling are exclusive: clear one first; likewise
+ * gcr_problem_set_probabilities on a PROSAC problem).  GCR_FLAG_GUIDED_STOP on
+ * a PROSAC problem is GCR_EINVAL.  gcr_solve_batch's items stay uniform. */
+int gcr_problem_set_prosac(gcr_problem* prob, uint64_t convergence_iterations);
 /* full estimator call on the resident problem (same semantics as gcr_rect_*) */
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
                     double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out);
@@ -451,7 +471,8 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
  * indices of attempt `attempt` of slots slot0 .. slot0 + nslots - 1 (idx_out:
  * as many per slot,
  * all-ones where the draw budget ran out), with the problem's sampler --
- * guided after gcr_problem_set_probabilities, else uniform */
+ * guided after gcr_problem_set_probabilities, PROSAC after
+ * gcr_problem_set_prosac, else uniform */
 int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
                        uint32_t* idx_out);
 /* measurement (tools/guided_bench.py): HIP-event time per launch, in ms, of
@@ -572,6 +593,17 @@ double gcr_host_atan2(double y, double x);
 double gcr_host_math(int op, double a, double b);
 int gcr_host_sample(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls, uint64_t n,
                     uint32_t m, uint32_t* out);
+/* host-only: PROSAC's growth table (csrc/prosac.h) of n rows, minimal sample
+ * m <= 32 and convergence length 1 .. 2^40: g_out[0 .. n], the entries below
+ * m are 0 */
+int gcr_host_prosac_growth(size_t n, uint32_t m, uint64_t convergence, uint64_t* g_out);
+/* host-only: the pool size n(slot + 1) of a slot by the flat search over that
+ * table; *pool_out = 0 in the uniform phase (slot >= g[n]) */
+int gcr_host_prosac_pool(size_t n, uint32_t m, uint64_t convergence, uint64_t slot, uint32_t* pool_out);
+/* host-only: one PROSAC sample, the generators' function: attempt `sub` of
+ * slot `index` (main stream, class 0), m indices in out */
+int gcr_host_sample_prosac(uint64_t seed, uint64_t index, uint32_t sub, size_t n, uint32_t m, uint64_t convergence,
+                           uint32_t* out);
 /* host-only: the check gcr_problem_set_probabilities makes of its weights for
  * a minimal sample of m (GCR_OK, or GCR_EINVAL with a message) */
 int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m);
