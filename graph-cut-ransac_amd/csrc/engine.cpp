@@ -52,6 +52,7 @@
 #include "gcr.h"
 #include "host_fit.h"
 #include "guided_stop.h"
+#include "prosac_stop.h"
 #include "kernels.h"
 #include "fm_groups.h"
 #include "philox.h"
@@ -343,14 +344,22 @@ struct Workspace {
     // PROSAC sampling: the problem's growth table (prosac.h, N + 1 entries),
     // under the same lifetime rule
     DevBuf<uint64_t> prosac_tab;
-    // the guided stop's mass launches (RunnerT::inlier_masses): the models in
-    // pinned memory and on the device, each model's (count, mass) pinned
+    // the PROSAC stop's tables (prosac_stop.h, N + 1 entries each), read by a
+    // run's stop launches on the replay stream alone: Imin is uploaded with the
+    // growth table, qmin at the start of the first run of each confidence
+    DevBuf<uint32_t> prosac_imin;
+    DevBuf<double> prosac_qmin;
+    // the stop-measure launches of the guided and the PROSAC stop
+    // (RunnerT::stop_measures): the models in pinned memory and on the device,
+    // each model's (count, mass) or (count, best_i, best_n) pinned
     PinBuf<GeoModel> gm_hmodels;
     DevBuf<GeoModel> gm_models;
     DevBuf<uint32_t> gm_dcount;
     DevBuf<uint64_t> gm_dmass;
     PinBuf<uint32_t> gm_count;
     PinBuf<uint64_t> gm_mass;
+    DevBuf<uint32_t> gm_dbi, gm_dbn;
+    PinBuf<uint32_t> gm_bi, gm_bn;
     // score_models' completion flags (ScoreOut::done): the small scorer stores
     // done_epoch into lo_done[m] after model m's results; the results, list
     // bits and flags live in coherent pinned memory, so the host waits on the
@@ -608,6 +617,15 @@ struct gcr_problem {
     // gt.  Handed to the generator launches only.
     ProsacTable pt{};
     const ProsacTable* prosac() const { return pt.g ? &pt : nullptr; }
+    // the PROSAC stop (prosac_stop.h, GCR_FLAG_PROSAC_STOP): the growth table's
+    // host copy, kept for qmin; Imin in the workspace's prosac_imin since
+    // gcr_problem_set_prosac; qmin in prosac_qmin for the confidence whose
+    // log(1 - confidence) is ps_log_prob (ps_qmin null: none built yet).  Set
+    // and cleared with pt.
+    std::vector<uint64_t> ps_g;
+    const uint32_t* ps_imin = nullptr;
+    const double* ps_qmin = nullptr;
+    double ps_log_prob = 0.0;
     // Calibrated solvers: hc[0] and the device SoA hold the K-normalised
     // correspondences.  Host only: the pixel columns (the neighbourhood
     // grid is built over them) and the divisor that takes a pixel threshold
@@ -630,6 +648,23 @@ struct gcr_problem {
 };
 
 namespace {
+
+// The PROSAC stop's qmin table (prosac_stop.h) for log_prob on the device: N
+// glibc exp calls and one upload, made by the first run of each confidence and
+// kept on the problem while the confidence stays the same.  No stop launch of
+// an earlier run is in flight (every one is synchronised inside its run) and
+// generators never read the table, so a blocking copy suffices.
+void ensure_prosac_qmin(gcr_problem* P, double log_prob) {
+    if (P->pt.g == nullptr || P->ps_g.empty()) throw std::runtime_error("PROSAC stop: the problem has no growth table");
+    if (P->ps_qmin != nullptr && P->ps_log_prob == log_prob) return;
+    std::vector<double> q(P->ps_g.size());
+    prosac_stop_tables(P->ps_g.data(), P->pt.n, P->pt.m, log_prob, nullptr, q.data());
+    P->ps_qmin = nullptr;
+    P->w->prosac_qmin.ensure(q.size());
+    HIPC(hipMemcpy(P->w->prosac_qmin.p, q.data(), q.size() * sizeof(double), hipMemcpyHostToDevice));
+    P->ps_qmin = P->w->prosac_qmin.p;
+    P->ps_log_prob = log_prob;
+}
 
 // ---------------------------------------- decisions in glibc (exact.h) ----
 // The kernels evaluate the detmath twins and flag every decision whose twin
@@ -1978,6 +2013,9 @@ public:
         log_prob_ = std::log(1.0 - prm.confidence);
         do_lo_ = (prm.flags & GCR_FLAG_NO_LO) == 0;
         gstop_ = (prm.flags & GCR_FLAG_GUIDED_STOP) != 0;      // the entries checked it (check_guided_stop)
+        pstop_ = (prm.flags & GCR_FLAG_PROSAC_STOP) != 0;      // ... and it (check_prosac_stop)
+        mstop_ = gstop_ || pstop_;
+        if (pstop_) ensure_prosac_qmin(P, log_prob_);
         std::memset(&st_, 0, sizeof(st_));
         if (kRect && exact_) {
             sbnd_ = score_bound(Tm_, K_);
@@ -2108,14 +2146,14 @@ public:
                     bool nonmin = false;
                     for (int c = 0; c < K_; ++c) if (best_.n[c] > m_[c]) { nonmin = true; break; }
                     do_lo = (it_ > 20) && nonmin;
-                    if (gstop_) remass_best();          // this replay has no chain: one launch per new best
+                    if (mstop_) remeasure_best();       // this replay has no chain: one launch per new best
                     max_iteration = stop_number();
                 }
             }
             if (do_lo_ && do_lo) {
                 replay_ms += ms_since(t_rep);
                 ++lo_number_;
-                if (local_optimization(bufs_[off_]) && gstop_) remass_best();
+                if (local_optimization(bufs_[off_]) && mstop_) remeasure_best();
                 max_iteration = stop_number();
                 t_rep = Clock::now();
             }
@@ -2416,10 +2454,10 @@ public:
         std::vector<SumHyp> lasts(world_);
         std::vector<uint8_t> has_last(world_);
         std::vector<uint64_t> itb(world_ + 1), hb(world_ + 1), tgt(world_);
-        // guided stop: (count, mass) of S[r].cand[k] in cand_mass[r][k]
+        // measured stops: the measure of S[r].cand[k] in cand_mass[r][k]
         std::vector<Model> cand_models;
-        std::vector<MassRec> cand_flat;
-        std::vector<std::vector<MassRec>> cand_mass(world_);
+        std::vector<StopRec> cand_flat;
+        std::vector<std::vector<StopRec>> cand_mass(world_);
         // plan + issue the chunk after the last issued one; `it_lo`: iterations
         // before it (exact, or a lower bound: every slot adds at least one)
         const bool spec_ok = ahead_ok && speculate_on() && min_it < max_it && prm_.batch_slots == 0;
@@ -2469,15 +2507,15 @@ public:
             // the LO masks for 60-80 us).  LO rarely raises the threshold
             // again; if it does, the next chunk is issued after the replay.
             // Results are identical either way.
-            // guided stop: the masses of every rank's chain members in one
+            // measured stops: the measures of every rank's chain members in one
             // launch, before the walk (every rank holds all features and all
             // members' models: each computes them locally and identically)
-            if (gstop_) {
+            if (mstop_) {
                 cand_models.clear();
                 for (int r = 0; r < world_; ++r)
                     for (uint32_t k = 0; k < S[r].ncand; ++k) cand_models.push_back(model_of(S[r].cand[k]));
                 cand_flat.resize(cand_models.size());
-                inlier_masses(cand_models.data(), (uint32_t)cand_models.size(), cand_flat.data());
+                stop_measures(cand_models.data(), (uint32_t)cand_models.size(), cand_flat.data());
                 size_t at = 0;
                 for (int r = 0; r < world_; ++r) {
                     cand_mass[r].assign(cand_flat.begin() + at, cand_flat.begin() + at + S[r].ncand);
@@ -2493,7 +2531,7 @@ public:
                         const HScore sc = finish(rn, h.v0, h.v1, h.tot);
                         if (best_.sum < sc.sum)
                             spec_thr = std::min(
-                                spec_thr, std::max(min_it, gstop_ ? guided_number(cand_mass[r][S[r].ncand - 1].mass)
+                                spec_thr, std::max(min_it, mstop_ ? measure_number(cand_mass[r][S[r].ncand - 1])
                                                                   : iteration_number(sc.n)));
                     }
             if (ahead_ok && q.size() == 1 && (itb[world_] < min_it || (spec_ok && itb[world_] < spec_thr)) &&
@@ -2510,7 +2548,7 @@ public:
                 if (do_lo_ && slot_lo) {
                     const auto t_lo = Clock::now();
                     ++lo_number_;
-                    if (local_optimization(bufs_[off_]) && gstop_) remass_best();
+                    if (local_optimization(bufs_[off_]) && mstop_) remeasure_best();
                     max_iteration = stop_number();
                     lo_ms += ms_since(t_lo);
                 }
@@ -2525,11 +2563,11 @@ public:
                         // continues the chain from the last one (collective)
                         resummarise(c, r, S[r].resume_pos, S[r].resume_bar, nullptr, X.data());
                         S[r] = X[r];
-                        if (gstop_) {                       // the continued chain's members: their own launch
+                        if (mstop_) {                       // the continued chain's members: their own launch
                             cand_models.clear();
                             for (uint32_t q2 = 0; q2 < S[r].ncand; ++q2) cand_models.push_back(model_of(S[r].cand[q2]));
                             cand_mass[r].resize(S[r].ncand);
-                            inlier_masses(cand_models.data(), S[r].ncand, cand_mass[r].data());
+                            stop_measures(cand_models.data(), S[r].ncand, cand_mass[r].data());
                         }
                         k = 0;
                         continue;
@@ -2573,9 +2611,9 @@ public:
                         bool nonmin = false;
                         for (int cc = 0; cc < K_; ++cc) if (best_.n[cc] > m_[cc]) { nonmin = true; break; }
                         slot_lo = (it_ > 20) && nonmin;
-                        if (gstop_) {
-                            check_mass(cand_mass[r][k - 1], best_.n[0]);
-                            best_mass_ = cand_mass[r][k - 1].mass;
+                        if (mstop_) {
+                            check_measure(cand_mass[r][k - 1], best_.n[0]);
+                            best_meas_ = cand_mass[r][k - 1];
                         }
                         max_iteration = stop_number();
                     }
@@ -3261,73 +3299,110 @@ private:
         return static_cast<uint64_t>(std::ceil(log_prob_ / lg));
     }
 
-    // ---- guided stop (GCR_FLAG_GUIDED_STOP, guided_stop.h) ----------------
-    // max_iteration from the current best's inlier MASS instead of its count.
-    // best_mass_ follows best_: a chain member's mass comes from its chunk's
-    // one launch (replay_summaries), a best found by LO gets a launch of its own.
-    bool gstop_ = false;
-    uint64_t best_mass_ = 0;
-    struct MassRec {
-        uint32_t count;
-        uint64_t mass;
+    // ---- measured stops (guided_stop.h, prosac_stop.h) ---------------------
+    // max_iteration from a measure of the current best other than its inlier
+    // count: its inlier MASS (GCR_FLAG_GUIDED_STOP) or its chosen prefix
+    // (I*, n*) (GCR_FLAG_PROSAC_STOP).  The entries allow one of the two at
+    // most.  best_meas_ follows best_: a chain member's measure comes from its
+    // chunk's one launch (replay_summaries), a best found by LO gets a launch
+    // of its own.
+    bool gstop_ = false, pstop_ = false;
+    bool mstop_ = false;                // either of them
+    struct StopRec {
+        uint32_t count;                 // the kernel's inlier count: the scorer's n0
+        uint64_t mass;                  // guided stop
+        uint32_t best_i, best_n;        // PROSAC stop
     };
-    // (count, mass) of nm models: one launch and one synchronisation on the
+    StopRec best_meas_{};
+    // the measure of nm models: one launch and one synchronisation on the
     // replay stream
-    void inlier_masses(const Model* models, uint32_t nm, MassRec* out) {
+    void stop_measures(const Model* models, uint32_t nm, StopRec* out) {
         if constexpr (!kRect) {
             if (nm == 0) return;
             Workspace* w = P_->w;
             const size_t cap = std::max<size_t>(nm, 64);
+            const uint32_t m = (uint32_t)m_[0];
             w->gm_hmodels.ensure(cap);
             w->gm_count.ensure(cap);
-            w->gm_mass.ensure(cap);
+            if (pstop_) {
+                w->gm_bi.ensure(cap);
+                w->gm_bn.ensure(cap);
+            } else {
+                w->gm_mass.ensure(cap);
+            }
             std::memcpy(w->gm_hmodels.p, models, (size_t)nm * sizeof(Model));
+            auto d2h = [&](void* dst, const void* src, size_t bytes) {
+                HIPC(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, s_));
+            };
             if (zerocopy_on()) {
                 // models read in place, results written straight to pinned memory
-                HIPC(launch_inlier_mass_geo(P_->dp, Tm_[0], dev_view(w->gm_hmodels.p), nm, P_->gq,
-                                            dev_view(w->gm_count.p), dev_view(w->gm_mass.p), s_));
+                if (pstop_)
+                    HIPC(launch_prosac_stop_geo(P_->dp, Tm_[0], dev_view(w->gm_hmodels.p), nm, m, P_->ps_imin,
+                                                P_->ps_qmin, dev_view(w->gm_count.p), dev_view(w->gm_bi.p),
+                                                dev_view(w->gm_bn.p), s_));
+                else
+                    HIPC(launch_inlier_mass_geo(P_->dp, Tm_[0], dev_view(w->gm_hmodels.p), nm, P_->gq,
+                                                dev_view(w->gm_count.p), dev_view(w->gm_mass.p), s_));
             } else {
                 w->gm_models.ensure(cap);
                 w->gm_dcount.ensure(cap);
-                w->gm_dmass.ensure(cap);
                 HIPC(hipMemcpyAsync(w->gm_models.p, w->gm_hmodels.p, (size_t)nm * sizeof(Model),
                                     hipMemcpyHostToDevice, s_));
-                HIPC(launch_inlier_mass_geo(P_->dp, Tm_[0], w->gm_models.p, nm, P_->gq, w->gm_dcount.p,
-                                            w->gm_dmass.p, s_));
-                HIPC(hipMemcpyAsync(w->gm_count.p, w->gm_dcount.p, (size_t)nm * sizeof(uint32_t),
-                                    hipMemcpyDeviceToHost, s_));
-                HIPC(hipMemcpyAsync(w->gm_mass.p, w->gm_dmass.p, (size_t)nm * sizeof(uint64_t),
-                                    hipMemcpyDeviceToHost, s_));
+                if (pstop_) {
+                    w->gm_dbi.ensure(cap);
+                    w->gm_dbn.ensure(cap);
+                    HIPC(launch_prosac_stop_geo(P_->dp, Tm_[0], w->gm_models.p, nm, m, P_->ps_imin, P_->ps_qmin,
+                                                w->gm_dcount.p, w->gm_dbi.p, w->gm_dbn.p, s_));
+                    d2h(w->gm_bi.p, w->gm_dbi.p, (size_t)nm * sizeof(uint32_t));
+                    d2h(w->gm_bn.p, w->gm_dbn.p, (size_t)nm * sizeof(uint32_t));
+                } else {
+                    w->gm_dmass.ensure(cap);
+                    HIPC(launch_inlier_mass_geo(P_->dp, Tm_[0], w->gm_models.p, nm, P_->gq, w->gm_dcount.p,
+                                                w->gm_dmass.p, s_));
+                    d2h(w->gm_mass.p, w->gm_dmass.p, (size_t)nm * sizeof(uint64_t));
+                }
+                d2h(w->gm_count.p, w->gm_dcount.p, (size_t)nm * sizeof(uint32_t));
             }
             HIPC(hipStreamSynchronize(s_));
-            for (uint32_t k = 0; k < nm; ++k) out[k] = MassRec{w->gm_count.p[k], w->gm_mass.p[k]};
+            for (uint32_t k = 0; k < nm; ++k)
+                out[k] = pstop_ ? StopRec{w->gm_count.p[k], 0, w->gm_bi.p[k], w->gm_bn.p[k]}
+                                : StopRec{w->gm_count.p[k], w->gm_mass.p[k], 0, 0};
             st_.launches += 1;
         } else {
             (void)models;
             (void)nm;
             (void)out;
-            throw std::runtime_error("guided stop: not a correspondence problem");
+            throw std::runtime_error("measured stop: not a correspondence problem");
         }
     }
     // the stop uses the inlier set the score used, or not at all
-    void check_mass(const MassRec& r, uint64_t n0) const {
+    void check_measure(const StopRec& r, uint64_t n0) const {
+        const char* who = pstop_ ? "PROSAC stop: the stop kernel" : "guided stop: the mass kernel";
         if (r.count != n0)
-            throw std::runtime_error("guided stop: the mass kernel counted " + std::to_string(r.count) +
+            throw std::runtime_error(std::string(who) + " counted " + std::to_string(r.count) +
                                      " inliers where the scorer counted " + std::to_string(n0));
-        if (r.mass > P_->gQ) throw std::runtime_error("guided stop: an inlier mass above the total");
+        if (pstop_) {
+            // a prefix of the rows holding no more inliers than rows, and no worse than (I_N, N)
+            if (r.best_n == 0 || r.best_n > N_[0] || r.best_i > r.best_n || r.best_i > r.count ||
+                (uint64_t)r.best_i * N_[0] < (uint64_t)r.count * r.best_n)
+                throw std::runtime_error("PROSAC stop: a chosen prefix outside the definition");
+        } else if (r.mass > P_->gQ) {
+            throw std::runtime_error("guided stop: an inlier mass above the total");
+        }
     }
-    // the mass of best_ after it changed outside a chunk's chain (LO)
-    void remass_best() {
-        MassRec r{};
-        inlier_masses(&best_val_, 1, &r);
-        check_mass(r, best_.n[0]);
-        best_mass_ = r.mass;
+    // the measure of best_ after it changed outside a chunk's chain (LO)
+    void remeasure_best() {
+        StopRec r{};
+        stop_measures(&best_val_, 1, &r);
+        check_measure(r, best_.n[0]);
+        best_meas_ = r;
     }
-    uint64_t guided_number(uint64_t mass) const {
-        return iteration_number_guided(mass, P_->gQ, (uint32_t)m_[0], log_prob_);
+    uint64_t measure_number(const StopRec& r) const {
+        return pstop_ ? iteration_number_prosac(r.best_i, r.best_n, (uint32_t)m_[0], log_prob_)
+                      : iteration_number_guided(r.mass, P_->gQ, (uint32_t)m_[0], log_prob_);
     }
     // max_iteration of the current best
-    uint64_t stop_number() const { return gstop_ ? guided_number(best_mass_) : iteration_number(best_.n); }
+    uint64_t stop_number() const { return mstop_ ? measure_number(best_meas_) : iteration_number(best_.n); }
 
     // Generate [s0, s0+B), then score only the slots the loop can still reach
     // (iterations can never pass max(min_it, max_it)).  Returns slots scored.
@@ -4455,13 +4530,29 @@ int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
                                    "problems only");
     if (prob->pt.g != nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem samples with PROSAC "
-                                   "(gcr_problem_set_prosac), whose stop is the uniform bound");
+                                   "(gcr_problem_set_prosac), whose own stop is GCR_FLAG_PROSAC_STOP");
     if (prob->gt.cdf == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
                                    "(gcr_problem_set_probabilities)");
     if (prob->gQ == 0)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP: guided sampling's weights are too many and too small to "
                                    "measure (every share is below 2^-%d)", guided_quanta_shift(prob->hc[0].n));
+    return GCR_OK;
+}
+
+// GCR_FLAG_PROSAC_STOP is valid only on a problem that samples with PROSAC,
+// and not together with the guided stop
+int check_prosac_stop(const gcr_problem* prob, const gcr_params* params) {
+    if ((params->flags & GCR_FLAG_PROSAC_STOP) == 0) return GCR_OK;
+    if ((params->flags & GCR_FLAG_GUIDED_STOP) != 0)
+        return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP and GCR_FLAG_GUIDED_STOP are exclusive: a problem samples "
+                                   "guided or with PROSAC, never both");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP: PROSAC sampling exists for correspondence problems only "
+                                   "(homography, SIFT homography, fundamental and essential matrix)");
+    if (prob->pt.g == nullptr)
+        return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP needs PROSAC sampling: the problem samples %s "
+                                   "(gcr_problem_set_prosac)", prob->gt.cdf ? "guided" : "uniformly");
     return GCR_OK;
 }
 
@@ -4534,6 +4625,7 @@ int set_prosac(gcr_problem* prob, uint64_t convergence) {
                                    "fundamental and essential matrix)");
     const size_t n = prob->hc[0].n, m = minimal_size(prob->solver);
     std::vector<uint64_t> g;
+    std::vector<uint32_t> imin;
     if (convergence != 0) {
         if (convergence > kProsacMaxConvergence)
             return set_err(GCR_EINVAL, "PROSAC sampling: convergence_iterations %llu is above 2^40",
@@ -4545,6 +4637,9 @@ int set_prosac(gcr_problem* prob, uint64_t convergence) {
             return set_err(GCR_EINVAL, "PROSAC sampling: %zu correspondences, a minimal sample takes %zu", n, m);
         g.resize(n + 1);
         prosac_growth((uint32_t)n, (uint32_t)m, convergence, g.data());
+        // the PROSAC stop's Imin (prosac_stop.h); its qmin waits for a run's confidence
+        imin.resize(n + 1);
+        prosac_stop_tables(g.data(), (uint32_t)n, (uint32_t)m, 0.0, imin.data(), nullptr);
     }
     return guard([&]() -> int {
         HIPC(hipSetDevice(prob->ctx->device));
@@ -4552,13 +4647,20 @@ int set_prosac(gcr_problem* prob, uint64_t convergence) {
         HIPC(hipStreamSynchronize(prob->ctx->side));
         HIPC(hipStreamSynchronize(prob->ctx->stream));
         prob->pt = ProsacTable{};
+        prob->ps_g.clear();
+        prob->ps_imin = nullptr;
+        prob->ps_qmin = nullptr;
         if (convergence == 0) return GCR_OK;
         prob->w->prosac_tab.ensure(g.size());
         HIPC(hipMemcpy(prob->w->prosac_tab.p, g.data(), g.size() * sizeof(uint64_t), hipMemcpyHostToDevice));
+        prob->w->prosac_imin.ensure(imin.size());
+        HIPC(hipMemcpy(prob->w->prosac_imin.p, imin.data(), imin.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+        prob->ps_imin = prob->w->prosac_imin.p;
         prob->pt.g = prob->w->prosac_tab.p;
         prob->pt.n = (uint32_t)n;
         prob->pt.m = (uint32_t)m;
         prob->pt.g_n = g[n];
+        prob->ps_g = std::move(g);
         return GCR_OK;
     });
 }
@@ -4760,6 +4862,7 @@ int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_
                     double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out) {
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_prosac_stop(prob, params)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
     if (int e = check_sift_rows(prob)) return e;
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
@@ -4779,6 +4882,7 @@ int gcr_problem_run_sharded(gcr_problem* prob, const gcr_params* params, int ran
                             double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out) {
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_prosac_stop(prob, params)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
     if (int e = check_sift_rows(prob)) return e;
     if (world < 1 || rank < 0 || rank >= world || (world > 1 && !allgather))
@@ -4852,6 +4956,7 @@ int gcr_problem_run_comm(gcr_problem* prob, const gcr_params* params, gcr_comm* 
     if (!prob || !comm) return set_err(GCR_EINVAL, "null problem or communicator");
     if (comm->ctx != prob->ctx) return set_err(GCR_EINVAL, "communicator and problem on different contexts");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_prosac_stop(prob, params)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
     if (int e = check_sift_rows(prob)) return e;
     if (!mask0_out || !H_out || (prob->K == 2 && !mask1_out)) return set_err(GCR_EINVAL, "null output buffer");
@@ -4890,6 +4995,7 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
                                uint32_t nbatches, gcr_batch_result* out, gcr_stats* stats_out) {
     if (!prob || !out) return set_err(GCR_EINVAL, "null problem or output");
     if (int e = check_params(params, prob->solver)) return e;
+    if (int e = check_prosac_stop(prob, params)) return e;
     if (int e = check_guided_stop(prob, params)) return e;
     if (int e = check_sift_rows(prob)) return e;
     if (nslots == 0 || nbatches == 0) return set_err(GCR_EINVAL, "nslots and nbatches must be > 0");
@@ -4917,6 +5023,9 @@ static int run_oneshot(gcr_ctx* ctx, int solver, const double* f0, size_t n0, co
                        const double* sift = nullptr) {
     if (!ctx) return set_err(GCR_EINVAL, "null context");
     if (int e = check_params(params, solver)) return e;
+    if ((params->flags & GCR_FLAG_PROSAC_STOP) != 0)
+        return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP needs PROSAC sampling: the one-shot entries and "
+                                   "gcr_solve_batch's items sample uniformly or guided");
     if ((params->flags & GCR_FLAG_GUIDED_STOP) != 0 && probabilities == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the plain entries and "
                                    "gcr_solve_batch's items carry no probabilities");
@@ -5470,6 +5579,41 @@ int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const d
     });
 }
 
+int gcr_debug_prosac_stop_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels,
+                            uint32_t* count_out, uint32_t* best_i_out, uint32_t* best_n_out) {
+    if (!prob || !params || !H || !count_out || !best_i_out || !best_n_out)
+        return set_err(GCR_EINVAL, "null argument");
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "not a correspondence (homography / fundamental / essential) problem");
+    if (prob->pt.g == nullptr)
+        return set_err(GCR_EINVAL, "the PROSAC stop needs PROSAC sampling (gcr_problem_set_prosac)");
+    if (!(params->confidence > 0.0 && params->confidence < 1.0))
+        return set_err(GCR_EINVAL, "confidence must be in (0, 1)");
+    if (nmodels == 0) return GCR_OK;
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        hipStream_t s = prob->ctx->stream;
+        const double thr = prob->thr0(*params);
+        const double T = (2.25 * thr) * thr;
+        ensure_prosac_qmin(prob, std::log(1.0 - params->confidence));
+        Workspace* w = prob->w;
+        w->gm_models.ensure(nmodels);
+        w->gm_dcount.ensure(nmodels);
+        w->gm_dbi.ensure(nmodels);
+        w->gm_dbn.ensure(nmodels);
+        HIPC(hipMemcpyAsync(w->gm_models.p, H, (size_t)nmodels * sizeof(GeoModel), hipMemcpyHostToDevice, s));
+        HIPC(launch_prosac_stop_geo(prob->dp, T, w->gm_models.p, nmodels, (uint32_t)minimal_size(prob->solver),
+                                    prob->ps_imin, prob->ps_qmin, w->gm_dcount.p, w->gm_dbi.p, w->gm_dbn.p, s));
+        const size_t bytes = (size_t)nmodels * sizeof(uint32_t);
+        HIPC(hipMemcpyAsync(count_out, w->gm_dcount.p, bytes, hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(best_i_out, w->gm_dbi.p, bytes, hipMemcpyDeviceToHost, s));
+        HIPC(hipMemcpyAsync(best_n_out, w->gm_dbn.p, bytes, hipMemcpyDeviceToHost, s));
+        HIPC(hipStreamSynchronize(s));
+        return GCR_OK;
+    });
+}
+
 int gcr_host_fit_h(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* H_out) {
     return host_fit_corr(kKindHomography, correspondences, n, idx, k, H_out, fit_h4_nonminimal);
 }
@@ -5762,6 +5906,36 @@ int gcr_host_prosac_pool(size_t n, uint32_t m, uint64_t convergence, uint64_t sl
         *pool_out = prosac_pool_flat(g.data(), (uint32_t)n, m, slot);
         return GCR_OK;
     });
+}
+
+int gcr_host_prosac_stop_tables(size_t n, uint32_t m, uint64_t convergence, double confidence, uint32_t* imin_out,
+                                double* qmin_out) {
+    if (!imin_out || !qmin_out) return set_err(GCR_EINVAL, "null output");
+    if (int e = check_prosac_args(n, m, convergence)) return e;
+    if (!(confidence > 0.0 && confidence < 1.0)) return set_err(GCR_EINVAL, "confidence must be in (0, 1)");
+    return guard([&]() -> int {
+        std::vector<uint64_t> g(n + 1);
+        prosac_growth((uint32_t)n, m, convergence, g.data());
+        prosac_stop_tables(g.data(), (uint32_t)n, m, std::log(1.0 - confidence), imin_out, qmin_out);
+        return GCR_OK;
+    });
+}
+
+int gcr_host_prosac_stop(const uint8_t* mask, size_t n, uint32_t m, const uint32_t* imin, const double* qmin,
+                         uint32_t* best_i, uint32_t* best_n) {
+    if (!mask || !imin || !qmin || !best_i || !best_n) return set_err(GCR_EINVAL, "null argument");
+    if (int e = check_prosac_args(n, m, 1)) return e;
+    prosac_stop_choose(mask, (uint32_t)n, m, imin, qmin, best_i, best_n);
+    return GCR_OK;
+}
+
+int gcr_host_prosac_stop_number(uint32_t best_i, uint32_t best_n, uint32_t m, double confidence, uint64_t* out) {
+    if (!out) return set_err(GCR_EINVAL, "null output");
+    if (best_n == 0 || best_i > best_n || m < 1 || m > 32)
+        return set_err(GCR_EINVAL, "PROSAC stop: need 0 <= best_i <= best_n, best_n >= 1 and 1 <= m <= 32");
+    if (!(confidence > 0.0 && confidence < 1.0)) return set_err(GCR_EINVAL, "confidence must be in (0, 1)");
+    *out = iteration_number_prosac(best_i, best_n, m, std::log(1.0 - confidence));
+    return GCR_OK;
 }
 
 int gcr_host_sample_prosac(uint64_t seed, uint64_t index, uint32_t sub, size_t n, uint32_t m, uint64_t convergence,

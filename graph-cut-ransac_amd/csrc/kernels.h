@@ -332,6 +332,14 @@ hipError_t launch_select_geo(int solver, const ScoreOut& sc, const uint8_t* inc,
 // are exact integers, the same for every reduction order.
 hipError_t launch_inlier_mass_geo(const DevProblem& p, double T, const GeoModel* models, uint32_t nmodels,
                                   const uint64_t* quanta, uint32_t* count, uint64_t* mass, hipStream_t stream);
+// The PROSAC stop's measure of `nmodels` models (prosac_stop.h): count[k] as
+// above, (best_i[k], best_n[k]) the chosen prefix (I*, n*) of models[k] under
+// the tables imin / qmin (N + 1 entries each in device memory) for minimal
+// sample m.  One workgroup per model walks the rows in rank order; no atomics,
+// and the choice's order is total, so the result is the host twin's.
+hipError_t launch_prosac_stop_geo(const DevProblem& p, double T, const GeoModel* models, uint32_t nmodels, uint32_t m,
+                                  const uint32_t* imin, const double* qmin, uint32_t* count, uint32_t* best_i,
+                                  uint32_t* best_n, hipStream_t stream);
 // deferred selection of `count` consecutive batches in one launch (one
 // workgroup per batch): batch b's score arrays, inc, hmap at offset b * stride,
 // its hcount at hcount + b, its slots from slot0 + b * nh / per, its record out[b]

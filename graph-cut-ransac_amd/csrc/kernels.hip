@@ -20,6 +20,7 @@
 #include "guided.h"
 #include "philox.h"
 #include "prosac.h"
+#include "prosac_stop.h"
 #include "qr3.h"
 #include "sifth.h"
 
@@ -5790,6 +5791,108 @@ hipError_t launch_inlier_mass_geo(const DevProblem& p, double T, const GeoModel*
     const dim3 grid(nmodels), block(kScoreBlock);
     if (p.kind == kKindFundamental) hipLaunchKernelGGL(k_inlier_mass<4>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
     else hipLaunchKernelGGL(k_inlier_mass<3>, grid, block, 0, stream, p.cls[0], T, models, quanta, count, mass);
+    return hipGetLastError();
+}
+
+// the PROSAC stop's choice (prosac_stop.h) of each model: one workgroup per
+// model takes the rows in tiles of kScoreBlock consecutive rows, thread t the
+// row tile * kScoreBlock + t, so lane order is rank order.  A wave's ballot
+// gives every lane its inclusive prefix (the popcount of the ballot at and
+// below the lane); the waves' totals go through LDS (two buffers: a wave may
+// write tile k + 2's only after every wave has passed tile k + 1's barrier,
+// hence read tile k's) and the tile total carries in a register.  With I_n in
+// hand a thread tests its prefix and keeps its best under the definition's
+// total order; the final reduction (shuffles, then LDS) starts from (I_N, N).
+template <int KIND>
+__global__ __launch_bounds__(kScoreBlock) void k_prosac_stop(DevClass c, double T, const GeoModel* __restrict__ models,
+                                                             uint32_t m, const uint32_t* __restrict__ imin,
+                                                             const double* __restrict__ qmin,
+                                                             uint32_t* __restrict__ count,
+                                                             uint32_t* __restrict__ best_i,
+                                                             uint32_t* __restrict__ best_n) {
+    constexpr int kWaves = kScoreBlock / 64;
+    __shared__ uint32_t s_tot[2][kWaves];
+    __shared__ uint32_t s_bi[kWaves];
+    __shared__ uint32_t s_bn[kWaves];
+    const GeoModel mdl = models[blockIdx.x];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t n = c.n;
+    const uint32_t first = prosac_stop_first(m);
+    const uint64_t below = lane == 63 ? ~0ull : ((1ull << (lane + 1)) - 1ull);
+    uint32_t carry = 0;                 // inliers of the tiles before this one
+    uint32_t bi = 0, bn = 1;            // below every candidate: (I_N, N), N >= 2, comes before it
+    const uint64_t tiles = (n + kScoreBlock - 1) / kScoreBlock;
+    for (uint64_t tile = 0; tile < tiles; ++tile) {
+        const uint64_t i = tile * kScoreBlock + threadIdx.x;
+        bool inl = false;
+        if (i < n) inl = geo_sq_residual<KIND>(c.x[i], c.y[i], c.a[i], c.c0[i], mdl.h) <= T;
+        const uint64_t bal = __ballot(inl);
+        const int b = (int)(tile & 1);
+        if (lane == 0) s_tot[b][wave] = (uint32_t)__popcll(bal);
+        __syncthreads();
+        uint32_t before = carry, total = 0;
+#pragma unroll
+        for (int k = 0; k < kWaves; ++k) {
+            const uint32_t t = s_tot[b][k];
+            before += k < wave ? t : 0u;
+            total += t;
+        }
+        carry += total;
+        const uint32_t I = before + (uint32_t)__popcll(bal & below);
+        const uint64_t len = i + 1;     // the prefix this row closes
+        if (len >= first && len < n) {
+            const uint32_t ln = (uint32_t)len;
+            if (prosac_stop_feasible(I, ln, m, imin[ln], qmin[ln]) && prosac_stop_better(I, ln, bi, bn)) {
+                bi = I;
+                bn = ln;
+            }
+        }
+    }
+    if (prosac_stop_better(carry, (uint32_t)n, bi, bn)) {
+        bi = carry;
+        bn = (uint32_t)n;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) {
+        const uint32_t oi = (uint32_t)__shfl_xor((int)bi, d), on = (uint32_t)__shfl_xor((int)bn, d);
+        if (prosac_stop_better(oi, on, bi, bn)) {
+            bi = oi;
+            bn = on;
+        }
+    }
+    if (lane == 0) {
+        s_bi[wave] = bi;
+        s_bn[wave] = bn;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (int k = 1; k < kWaves; ++k)
+            if (prosac_stop_better(s_bi[k], s_bn[k], bi, bn)) {
+                bi = s_bi[k];
+                bn = s_bn[k];
+            }
+        count[blockIdx.x] = carry;
+        best_i[blockIdx.x] = bi;
+        best_n[blockIdx.x] = bn;
+    }
+}
+
+hipError_t launch_prosac_stop_geo(const DevProblem& p, double T, const GeoModel* models, uint32_t nmodels, uint32_t m,
+                                  const uint32_t* imin, const double* qmin, uint32_t* count, uint32_t* best_i,
+                                  uint32_t* best_n, hipStream_t stream) {
+    if (nmodels == 0) return hipSuccess;
+    if (p.kind != kKindHomography && p.kind != kKindFundamental) return hipErrorInvalidValue;
+    if (models == nullptr || imin == nullptr || qmin == nullptr || count == nullptr || best_i == nullptr ||
+        best_n == nullptr)
+        return hipErrorInvalidValue;
+    // the choice's products and (uint32_t)(row + 1) need N < 2^32; N >= 2 for the starting pair
+    if (m < 1 || p.cls[0].n < 2 || p.cls[0].n >= 0xffffffffull) return hipErrorInvalidValue;
+    const dim3 grid(nmodels), block(kScoreBlock);
+    if (p.kind == kKindFundamental)
+        hipLaunchKernelGGL(k_prosac_stop<4>, grid, block, 0, stream, p.cls[0], T, models, m, imin, qmin, count, best_i, best_n);
+    else
+        hipLaunchKernelGGL(k_prosac_stop<3>, grid, block, 0, stream, p.cls[0], T, models, m, imin, qmin, count, best_i, best_n);
     return hipGetLastError();
 }
 

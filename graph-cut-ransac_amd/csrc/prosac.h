@@ -27,8 +27,10 @@
 //           indices, the uniform sampler's own bits for that slot.
 //
 // Only the sampler changes: the stop is the reference's uniform bound (valid,
-// since the sampler becomes the uniform one); PROSAC's own non-randomness /
-// maximality stop is not implemented.
+// since the sampler becomes the uniform one).  PROSAC's own non-randomness /
+// maximality stop is opt-in (GCR_FLAG_PROSAC_STOP) and defined in
+// prosac_stop.h; it reads this table's g[n] as the number of slots whose pool
+// lies within the first n rows.
 //
 // The generators do not search g in global memory per attempt.  A workgroup
 // covers at most kProsacWindow consecutive slots and g is strictly increasing,

@@ -26,6 +26,7 @@ SOLVER_ESSENTIAL3_GRAVITY = 6   # ... from gcr_problem_create_gravity_essential
 SOLVER_HOMOGRAPHY2_SIFT = 7     # ... from gcr_problem_create_sift_homography
 FLAG_NO_LO = 1
 FLAG_GUIDED_STOP = 2     # guided sampling only: the adaptive stop on the inlier mass (csrc/guided_stop.h)
+FLAG_PROSAC_STOP = 4     # PROSAC sampling only: the adaptive stop on the best-ranked prefix (csrc/prosac_stop.h)
 
 
 class Params(C.Structure):
@@ -222,6 +223,12 @@ def _load():
     L.gcr_host_prosac_pool.argtypes = [C.c_size_t, C.c_uint32, C.c_uint64, C.c_uint64, u32p]
     L.gcr_host_sample_prosac.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_size_t, C.c_uint32, C.c_uint64,
                                          u32p]
+    # the PROSAC stop (GCR_FLAG_PROSAC_STOP, csrc/prosac_stop.h): its host definition and its kernel alone
+    u8p = C.POINTER(C.c_uint8)
+    L.gcr_host_prosac_stop_tables.argtypes = [C.c_size_t, C.c_uint32, C.c_uint64, C.c_double, u32p, dp]
+    L.gcr_host_prosac_stop.argtypes = [u8p, C.c_size_t, C.c_uint32, u32p, dp, u32p, u32p]
+    L.gcr_host_prosac_stop_number.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, u64p]
+    L.gcr_debug_prosac_stop_h.argtypes = [vp, C.POINTER(Params), dp, C.c_uint32, u32p, u32p, u32p]
     # essential matrix (csrc/ess.h): pixel rows + calibration matrices
     L.gcr_find_essential_matrix.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Params), vp, vp,
                                             C.POINTER(Stats)]

@@ -256,7 +256,10 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     (gcr_problem_set_prosac, csrc/prosac.h) with that convergence length, the
     same on every rank: the rows are expected in quality order, best first, as
     in the C ABI.  A slot's pool is a function of the slot index alone, so the
-    sharded run stays bit-identical to the single-rank one.
+    sharded run stays bit-identical to the single-rank one.  With it,
+    ``params={"flags": _native.FLAG_PROSAC_STOP, ...}`` stops the run on
+    PROSAC's own bound (csrc/prosac_stop.h; every rank computes the chain
+    members' prefixes itself, as for the mass).
     Solver 5 (essential matrix) takes pixel rows and the calibration matrices
     `K1`, `K2` (3 x 3); its threshold is in pixels and H is E in normalised
     coordinates.  Solver 6 (essential matrix with known gravity) takes the

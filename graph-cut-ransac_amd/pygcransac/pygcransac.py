@@ -479,7 +479,7 @@ def _as_convergence(prosac_convergence):
 def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                          spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                          batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False, min_weights=None,
-                         create=None, prosac_convergence=100000):
+                         create=None, prosac_convergence=100000, prosac_stop=False):
     """min_weights: the minimal sample size the probabilities are checked for
     (default: min_rows).  create(ctx, rows, order, out): a resident problem of
     the estimator over `rows`, the caller's rows taken in `order` (sampler=1)."""
@@ -499,6 +499,9 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     if guided_stop and sampler_id != 3:
         raise ValueError("guided_stop=True stops on the guided sampler's inlier mass: it needs sampler=3 "
                          "with probabilities.")
+    if prosac_stop and sampler_id != 1:
+        raise ValueError("prosac_stop=True stops on PROSAC's best-ranked prefix: it needs sampler=1 with quality "
+                         "scores.")
     f = _as_features(correspondences)
     if f.ndim != 2:
         raise ValueError("Number of dimensions must be 2.")
@@ -511,6 +514,8 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     _set_grid(p, f, h1, w1, h2, w2, neighborhood_size)
     if guided_stop:
         p.flags |= N.FLAG_GUIDED_STOP
+    if prosac_stop:
+        p.flags |= N.FLAG_PROSAC_STOP
     mask = np.zeros(n, dtype=np.uint8)
     M = np.zeros(9, dtype=np.float64)
     st = N.Stats()
@@ -556,7 +561,7 @@ def _plain_create(solver):
 def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                    spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                    neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False, guided_stop=False,
-                   prosac_convergence=100000):
+                   prosac_convergence=100000, prosac_stop=False):
     """4-point homography with graph-cut LO -- an EXTENSION (SURVEY.md §8(f)
     row 3): this fork has no homography estimator (finding 0.1); the argument
     names and order follow upstream pygcransac's findHomography.
@@ -588,9 +593,13 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     keep their order), early iterations sample among the best-ranked rows, the
     pool grows on PROSAC's schedule of ``prosac_convergence`` iterations
     (1 .. 2^40) and past it every iteration is the uniform sampler's; the mask
-    comes back in the caller's order.  Only an order is needed, and the stop
-    stays the reference's uniform bound (PROSAC's own non-randomness /
-    maximality stop is not implemented); ``guided_stop`` does not apply.
+    comes back in the caller's order.  Only an order is needed.  The stop
+    stays the reference's uniform bound unless ``prosac_stop=True``
+    (``sampler=1`` only, else ValueError): then it is PROSAC's own
+    non-randomness / maximality stop (csrc/prosac_stop.h), the same bound on
+    the best model's inlier share over the best-ranked prefix that is
+    non-random and that the samples drawn so far cover; it can only end a run
+    sooner.  ``guided_stop`` does not apply.
     ``threshold`` is the inlier threshold in pixels
     of the second image (MSAC threshold 2.25 * threshold, as the rectification
     solvers).
@@ -601,13 +610,14 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
                                 h1, w1, h2, w2, probabilities, threshold, conf, spatial_coherence_weight, max_iters,
                                 min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
-                                create=_plain_create(N.SOLVER_HOMOGRAPHY4), prosac_convergence=prosac_convergence)
+                                create=_plain_create(N.SOLVER_HOMOGRAPHY4), prosac_convergence=prosac_convergence,
+                                prosac_stop=prosac_stop)
 
 
 def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                           spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50,
                           *, neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                          guided_stop=False, prosac_convergence=100000):
+                          guided_stop=False, prosac_convergence=100000, prosac_stop=False):
     """7-point fundamental matrix with graph-cut LO -- an EXTENSION like
     findHomography (same arguments, the same neighbourhood grid; upstream
     pygcransac's findFundamentalMatrix order).  The residual is the Sampson distance in pixels; a sample yields up
@@ -615,7 +625,7 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
     7 of them > 0) guides the 7-point samples as it does findHomography's, and
     ``guided_stop=True`` stops such a run on the inlier mass, as there;
     ``sampler=1`` with quality scores and ``prosac_convergence`` is PROSAC, as
-    there.
+    there, and ``prosac_stop=True`` its own stop.
 
     Returns ``(F, inliers)`` with F (3, 3), unit Frobenius norm and
     x2^T F x1 = 0, or ``(None, inliers)``.
@@ -624,7 +634,8 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
                                 correspondences, h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 7, neighborhood_size, guided_stop,
-                                create=_plain_create(N.SOLVER_FUNDAMENTAL7), prosac_convergence=prosac_convergence)
+                                create=_plain_create(N.SOLVER_FUNDAMENTAL7), prosac_convergence=prosac_convergence,
+                                prosac_stop=prosac_stop)
 
 
 def _as_calibration(K, name):
@@ -637,7 +648,7 @@ def _as_calibration(K, name):
 def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                         spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                         neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                        guided_stop=False, prosac_convergence=100000):
+                        guided_stop=False, prosac_convergence=100000, prosac_stop=False):
     """5-point essential matrix with graph-cut LO for calibrated cameras -- an
     EXTENSION like findFundamentalMatrix (upstream pygcransac's
     findEssentialMatrix order; csrc/ess.h is the solver's definition).
@@ -650,7 +661,8 @@ def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=N
     grid lies over the pixel coordinates, as findFundamentalMatrix's.  A sample
     yields up to ten models, each scored.  ``sampler``, ``probabilities`` (at
     least 5 of them > 0) and ``guided_stop`` as in findHomography, and so are
-    ``sampler=1`` (PROSAC: quality scores) and ``prosac_convergence``.
+    ``sampler=1`` (PROSAC: quality scores), ``prosac_convergence`` and
+    ``prosac_stop``.
 
     Returns ``(E, inliers)`` with E (3, 3), unit Frobenius norm and
     (K2^-1 x2)^T E (K1^-1 x1) = 0, or ``(None, inliers)``.
@@ -673,7 +685,8 @@ def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=N
     return _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                                 batch_slots, return_stats, 5, neighborhood_size, guided_stop, create=create,
-                                prosac_convergence=prosac_convergence)
+                                prosac_convergence=prosac_convergence,
+                                prosac_stop=prosac_stop)
 
 
 def _as_rotation(G, name):
@@ -687,7 +700,7 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
                                probabilities=None, threshold=1.0, conf=0.99, spatial_coherence_weight=0.975,
                                max_iters=10000, min_iters=50, sampler=0, lo_number=50, *, neighborhood_size=8, seed=0,
                                device=None, batch_slots=0, return_stats=False, guided_stop=False,
-                               prosac_convergence=100000):
+                               prosac_convergence=100000, prosac_stop=False):
     """3-point essential matrix with graph-cut LO for calibrated cameras whose
     gravity direction is known (a phone, a vehicle, any IMU rig) -- an
     EXTENSION like findEssentialMatrix (upstream pygcransac's
@@ -732,13 +745,14 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
     return _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                                 batch_slots, return_stats, 3, neighborhood_size, guided_stop, create=create,
-                                prosac_convergence=prosac_convergence)
+                                prosac_convergence=prosac_convergence,
+                                prosac_stop=prosac_stop)
 
 
 def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                        spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                        neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                       guided_stop=False, prosac_convergence=100000):
+                       guided_stop=False, prosac_convergence=100000, prosac_stop=False):
     """Homography from TWO SIFT correspondences with graph-cut LO -- an
     EXTENSION like findHomography (what upstream pygcransac's findHomography
     runs with its SIFT-based solver).  Upstream's solver is not part of this
@@ -785,4 +799,5 @@ def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, thre
     return _correspondence_call(entry, guided_entry, np.ascontiguousarray(f8[:, :4]), h1, w1, h2, w2, probabilities,
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
-                                min_weights=2, create=create, prosac_convergence=prosac_convergence)
+                                min_weights=2, create=create, prosac_convergence=prosac_convergence,
+                                prosac_stop=prosac_stop)

@@ -44,7 +44,8 @@ extern "C" {
  * (GCR_SOLVER_ESSENTIAL5) likewise: new functions and a new solver kind only;
  * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY), the
  * host hook gcr_host_guided_index, and the homography from two SIFT
- * correspondences (GCR_SOLVER_HOMOGRAPHY2_SIFT). */
+ * correspondences (GCR_SOLVER_HOMOGRAPHY2_SIFT).  PROSAC sampling and its
+ * stop (GCR_FLAG_PROSAC_STOP) likewise: a new flag bit and new functions. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -85,7 +86,7 @@ typedef struct gcr_params {
     double confidence;                   /* settings.h:60 default 0.95 (not set by Python) */
     uint64_t seed;                       /* extension: Philox key (reference is unseeded) */
     uint32_t batch_slots;                /* extension: outer-iteration slots per launch, 0 = auto */
-    uint32_t flags;                      /* GCR_FLAG_*: bit 0 disables local optimisation (bench only), bit 1 the guided stop */
+    uint32_t flags;                      /* GCR_FLAG_*: bit 0 disables local optimisation (bench only), bit 1 the guided stop, bit 2 the PROSAC stop */
     /* extension (homography / fundamental matrix only): the neighbourhood grid
      * over (x1, y1, x2, y2) whose cells give labeling()'s pairwise terms
      * (GridNeighborhoodGraph<4>, grid_neighborhood_graph.h:229-301); cell
@@ -107,6 +108,15 @@ typedef struct gcr_params {
  * (csrc/guided_stop.h is the definition).  With all-equal weights the two are
  * the same bits.  Clear (the default): the reference's uniform bound. */
 #define GCR_FLAG_GUIDED_STOP 2u
+/* PROSAC sampling only (a problem after gcr_problem_set_prosac; anything
+ * else -- a uniform or guided problem, the one-shot entries, gcr_solve_batch's
+ * items -- and both stop flags together are GCR_EINVAL): the adaptive stop
+ * uses the best model's inlier share I_n / n over the best-ranked prefix n*
+ * that is non-random and covered by the samples drawn so far, in place of
+ * I / N (csrc/prosac_stop.h is the definition).  n* = N is always allowed, so
+ * the flag can only lower max_iteration.  Clear (the default): the reference's
+ * uniform bound. */
+#define GCR_FLAG_PROSAC_STOP 4u
 
 /* model.h: NormalizingTransform{x0,y0,s}, RectifyingHomography{h7,h8},
  * ScaleBased{alpha}, OrientationBased{phi}. */
@@ -343,14 +353,16 @@ int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities
  * afterwards -- gcr_problem_run, _run_sharded, _run_comm, _verify_batch(es),
  * gcr_debug_generate_h, gcr_debug_sample_h, gcr_measure_generate_h -- uses
  * it; local optimisation's inner sampler stays uniform and the stop is the
- * uniform bound (PROSAC's own non-randomness / maximality stop is not
- * implemented).  convergence_iterations == 0 returns the problem to uniform
+ * uniform bound unless params->flags has GCR_FLAG_PROSAC_STOP: then it is
+ * PROSAC's own non-randomness / maximality stop (csrc/prosac_stop.h), whose
+ * Imin table is built here.  convergence_iterations == 0 returns the problem to uniform
  * sampling.  Either call first waits for a speculative chunk a previous run
  * left in flight.  GCR_EINVAL, the problem left as it was: rectification
  * problems, convergence_iterations > 2^40, a problem with probabilities set
  * (guided and PROSAC sampling are exclusive: clear one first; likewise
  * gcr_problem_set_probabilities on a PROSAC problem).  GCR_FLAG_GUIDED_STOP on
- * a PROSAC problem is GCR_EINVAL.  gcr_solve_batch's items stay uniform. */
+ * a PROSAC problem is GCR_EINVAL, as is GCR_FLAG_PROSAC_STOP on any other.
+ * gcr_solve_batch's items stay uniform. */
 int gcr_problem_set_prosac(gcr_problem* prob, uint64_t convergence_iterations);
 /* full estimator call on the resident problem (same semantics as gcr_rect_*) */
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
@@ -496,6 +508,13 @@ int gcr_debug_mask_h(gcr_problem* prob, const gcr_params* params, const double* 
  * gcr_debug_score_h's n0) and the sum of their quanta */
 int gcr_debug_inlier_mass_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels,
                             uint32_t* count_out, uint64_t* mass_out);
+/* the PROSAC stop's kernel alone (csrc/prosac_stop.h) on a problem that
+ * samples with PROSAC, at params' threshold and confidence: per model of H (9
+ * doubles each) the number of correspondences within the MSAC threshold
+ * 2.25 thr^2 (equal to gcr_debug_score_h's n0) and the chosen prefix
+ * (I*, n*) */
+int gcr_debug_prosac_stop_h(gcr_problem* prob, const gcr_params* params, const double* H, uint32_t nmodels,
+                            uint32_t* count_out, uint32_t* best_i_out, uint32_t* best_n_out);
 /* host-only: normalised least-squares homography of the listed
  * correspondences (the LO / final-refit fit); 1 = fitted, 0 = rejected */
 int gcr_host_fit_h(const double* correspondences, size_t n, const uint32_t* idx, size_t k, double* H_out);
@@ -604,6 +623,20 @@ int gcr_host_prosac_pool(size_t n, uint32_t m, uint64_t convergence, uint64_t sl
  * slot `index` (main stream, class 0), m indices in out */
 int gcr_host_sample_prosac(uint64_t seed, uint64_t index, uint32_t sub, size_t n, uint32_t m, uint64_t convergence,
                            uint32_t* out);
+/* host-only: the PROSAC stop's tables (csrc/prosac_stop.h) for n rows, minimal
+ * sample m, that growth table and `confidence`: imin_out[0 .. n] and
+ * qmin_out[0 .. n], the entries below m are 0 */
+int gcr_host_prosac_stop_tables(size_t n, uint32_t m, uint64_t convergence, double confidence, uint32_t* imin_out,
+                                double* qmin_out);
+/* host-only: the PROSAC stop's choice, the kernel's host twin: (I*, n*) of the
+ * inlier mask (n bytes in row order, nonzero = inlier) under those tables */
+int gcr_host_prosac_stop(const uint8_t* mask, size_t n, uint32_t m, const uint32_t* imin, const double* qmin,
+                         uint32_t* best_i, uint32_t* best_n);
+/* host-only: the PROSAC stop itself, the function the engine calls: the
+ * reference's iteration bound with ratio best_i / best_n for a minimal sample
+ * of m at `confidence` (UINT64_MAX where the reference's guard returns it).
+ * best_n == 0 or best_i > best_n: GCR_EINVAL */
+int gcr_host_prosac_stop_number(uint32_t best_i, uint32_t best_n, uint32_t m, double confidence, uint64_t* out);
 /* host-only: the check gcr_problem_set_probabilities makes of its weights for
  * a minimal sample of m (GCR_OK, or GCR_EINVAL with a message) */
 int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m);
