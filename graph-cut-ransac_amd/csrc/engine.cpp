@@ -53,6 +53,7 @@
 #include "host_fit.h"
 #include "guided_stop.h"
 #include "prosac_stop.h"
+#include "napsac_layers.h"
 #include "kernels.h"
 #include "fm_groups.h"
 #include "philox.h"
@@ -344,6 +345,10 @@ struct Workspace {
     // PROSAC sampling: the problem's growth table (prosac.h, N + 1 entries),
     // under the same lifetime rule
     DevBuf<uint64_t> prosac_tab;
+    // NAPSAC sampling: the problem's per-row records and the four layers'
+    // member lists (napsac.h), under the same lifetime rule
+    DevBuf<NapsacRecord> napsac_rec;
+    DevBuf<uint32_t> napsac_mem;
     // the PROSAC stop's tables (prosac_stop.h, N + 1 entries each), read by a
     // run's stop launches on the replay stream alone: Imin is uploaded with the
     // growth table, qmin at the start of the first run of each confidence
@@ -617,6 +622,12 @@ struct gcr_problem {
     // gt.  Handed to the generator launches only.
     ProsacTable pt{};
     const ProsacTable* prosac() const { return pt.g ? &pt : nullptr; }
+    // NAPSAC sampling (napsac.h, gcr_problem_set_napsac): the records and
+    // member lists in the workspace's napsac_rec / napsac_mem; nt.rec ==
+    // nullptr: not set.  Exclusive with gt and pt.  Handed to the generator
+    // launches only.
+    NapsacTable nt{};
+    const NapsacTable* napsac() const { return nt.rec ? &nt : nullptr; }
     // the PROSAC stop (prosac_stop.h, GCR_FLAG_PROSAC_STOP): the growth table's
     // host copy, kept for qmin; Imin in the workspace's prosac_imin since
     // gcr_problem_set_prosac; qmin in prosac_qmin for the confidence whose
@@ -648,6 +659,17 @@ struct gcr_problem {
 };
 
 namespace {
+
+// the four pixel columns the neighbourhood grid and NAPSAC's layers lie over
+// (calibrated problems keep them beside the normalised rows)
+void pixel_columns(const gcr_problem* prob, const double* cols[4]) {
+    const HostClass& c = prob->hc[0];
+    const bool px = is_ess(prob->solver);
+    cols[0] = px ? prob->pix[0].data() : c.x.data();
+    cols[1] = px ? prob->pix[1].data() : c.y.data();
+    cols[2] = px ? prob->pix[2].data() : c.a.data();
+    cols[3] = px ? prob->pix[3].data() : c.c0.data();
+}
 
 // The PROSAC stop's qmin table (prosac_stop.h) for log_prob on the device: N
 // glibc exp calls and one upload, made by the first run of each confidence and
@@ -1806,7 +1828,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static hipError_t generate(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, uint8_t* inc, Model* m,
                                hipStream_t s) {
         return launch_generate_geo(P->solver, P->dp, seed, s0, n, inc, m, s, P->guided(), P->grav(), P->sift(),
-                                   P->prosac());
+                                   P->prosac(), P->napsac());
     }
     static hipError_t score(gcr_problem* P, const double T[2], const Model* m, const uint8_t* inc, uint32_t n, bool,
                             const ScoreOut& out, hipStream_t s) {
@@ -1866,7 +1888,7 @@ struct GeoTraits {                 // homography (3) and fundamental matrix (4)
     static hipError_t verify_gen(gcr_problem* P, uint64_t seed, uint64_t s0, uint32_t n, const VBufs& b,
                                  hipStream_t s) {
         hipError_t e = launch_generate_geo(P->solver, P->dp, seed, s0, n, b.inc, b.models, s, P->guided(), P->grav(),
-                                           P->sift(), P->prosac());
+                                           P->sift(), P->prosac(), P->napsac());
         const uint32_t nh = n * (uint32_t)per(P);
         if (e == hipSuccess && b.hmap != nullptr && gen_compacts(nh))
             e = launch_compact(b.inc, nh, b.hmap, b.hcount, s);
@@ -3239,9 +3261,8 @@ private:
             if (solver_row(P_->solver).corr && prm_.cell_number > 0 && prm_.spatial_coherence_weight > 0) {
                 const HostClass& c = P_->hc[0];
                 // essential matrix: the grid lies over the pixels
-                const bool px = is_ess(P_->solver);
-                const double* cols[4] = {px ? P_->pix[0].data() : c.x.data(), px ? P_->pix[1].data() : c.y.data(),
-                                         px ? P_->pix[2].data() : c.a.data(), px ? P_->pix[3].data() : c.c0.data()};
+                const double* cols[4];
+                pixel_columns(P_, cols);
                 // a cell size of 0 (image size unknown to the caller): the
                 // column's extent (largest finite coordinate + 1, at least 1)
                 // over the cells, as pygcransac.grid_cell_sizes computes it
@@ -4531,6 +4552,9 @@ int check_guided_stop(const gcr_problem* prob, const gcr_params* params) {
     if (prob->pt.g != nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem samples with PROSAC "
                                    "(gcr_problem_set_prosac), whose own stop is GCR_FLAG_PROSAC_STOP");
+    if (prob->nt.rec != nullptr)
+        return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem samples with NAPSAC "
+                                   "(gcr_problem_set_napsac), whose stop is the uniform bound");
     if (prob->gt.cdf == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_GUIDED_STOP needs guided sampling: the problem has no probabilities "
                                    "(gcr_problem_set_probabilities)");
@@ -4550,6 +4574,9 @@ int check_prosac_stop(const gcr_problem* prob, const gcr_params* params) {
     if (!is_corr(prob->solver))
         return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP: PROSAC sampling exists for correspondence problems only "
                                    "(homography, SIFT homography, fundamental and essential matrix)");
+    if (prob->nt.rec != nullptr)
+        return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP needs PROSAC sampling: the problem samples with NAPSAC "
+                                   "(gcr_problem_set_napsac), whose stop is the uniform bound");
     if (prob->pt.g == nullptr)
         return set_err(GCR_EINVAL, "GCR_FLAG_PROSAC_STOP needs PROSAC sampling: the problem samples %s "
                                    "(gcr_problem_set_prosac)", prob->gt.cdf ? "guided" : "uniformly");
@@ -4575,6 +4602,9 @@ int set_probabilities(gcr_problem* prob, const double* w, size_t n) {
     if (w != nullptr && prob->pt.g != nullptr)
         return set_err(GCR_EINVAL, "probabilities: the problem samples with PROSAC; clear it first "
                                    "(gcr_problem_set_prosac(prob, 0))");
+    if (w != nullptr && prob->nt.rec != nullptr)
+        return set_err(GCR_EINVAL, "probabilities: the problem samples with NAPSAC; clear it first "
+                                   "(gcr_problem_set_napsac(prob, extent, 0))");
     std::vector<double> tab;
     GuidedTable t{};
     if (w != nullptr) {
@@ -4633,6 +4663,9 @@ int set_prosac(gcr_problem* prob, uint64_t convergence) {
         if (prob->gt.cdf != nullptr)
             return set_err(GCR_EINVAL, "PROSAC sampling: the problem has probabilities set (guided sampling); "
                                        "clear them first (gcr_problem_set_probabilities(prob, NULL, 0))");
+        if (prob->nt.rec != nullptr)
+            return set_err(GCR_EINVAL, "PROSAC sampling: the problem samples with NAPSAC; clear it first "
+                                       "(gcr_problem_set_napsac(prob, extent, 0))");
         if (n < m || n >= 0xffffffffull)
             return set_err(GCR_EINVAL, "PROSAC sampling: %zu correspondences, a minimal sample takes %zu", n, m);
         g.resize(n + 1);
@@ -4661,6 +4694,57 @@ int set_prosac(gcr_problem* prob, uint64_t convergence) {
         prob->pt.m = (uint32_t)m;
         prob->pt.g_n = g[n];
         prob->ps_g = std::move(g);
+        return GCR_OK;
+    });
+}
+
+// gcr_problem_set_napsac: set_prosac's order of things with napsac.h's layers.
+// Every check comes before the first change, so a refused call leaves the
+// problem as it was.
+int set_napsac(gcr_problem* prob, const double* extent, uint64_t iterations) {
+    if (!is_corr(prob->solver))
+        return set_err(GCR_EINVAL, "NAPSAC sampling: correspondence problems only (homography, SIFT homography, "
+                                   "fundamental and essential matrix)");
+    const size_t n = prob->hc[0].n, m = minimal_size(prob->solver);
+    NapsacLayers layers;
+    if (iterations != 0) {
+        if (iterations > kNapsacMaxIterations)
+            return set_err(GCR_EINVAL, "NAPSAC sampling: local_iterations %llu is above 2^40",
+                           (unsigned long long)iterations);
+        if (extent == nullptr || !napsac_extent_ok(extent))
+            return set_err(GCR_EINVAL, "NAPSAC sampling: the extents {w1, h1, w2, h2} must be positive and finite");
+        if (prob->gt.cdf != nullptr)
+            return set_err(GCR_EINVAL, "NAPSAC sampling: the problem has probabilities set (guided sampling); "
+                                       "clear them first (gcr_problem_set_probabilities(prob, NULL, 0))");
+        if (prob->pt.g != nullptr)
+            return set_err(GCR_EINVAL, "NAPSAC sampling: the problem samples with PROSAC; clear it first "
+                                       "(gcr_problem_set_prosac(prob, 0))");
+        if (n < m || n >= 0xffffffffull)
+            return set_err(GCR_EINVAL, "NAPSAC sampling: %zu correspondences, a minimal sample takes %zu", n, m);
+    }
+    return guard([&]() -> int {
+        if (iterations != 0) {
+            const double* cols[4];
+            pixel_columns(prob, cols);
+            napsac_layers(cols, n, extent, layers);
+        }
+        HIPC(hipSetDevice(prob->ctx->device));
+        await_spec(prob->w);
+        HIPC(hipStreamSynchronize(prob->ctx->side));
+        HIPC(hipStreamSynchronize(prob->ctx->stream));
+        prob->nt = NapsacTable{};
+        if (iterations == 0) return GCR_OK;
+        prob->w->napsac_rec.ensure(layers.rec.size());
+        HIPC(hipMemcpy(prob->w->napsac_rec.p, layers.rec.data(), layers.rec.size() * sizeof(NapsacRecord),
+                       hipMemcpyHostToDevice));
+        prob->w->napsac_mem.ensure(layers.members.size());
+        HIPC(hipMemcpy(prob->w->napsac_mem.p, layers.members.data(), layers.members.size() * sizeof(uint32_t),
+                       hipMemcpyHostToDevice));
+        prob->nt.rec = prob->w->napsac_rec.p;
+        prob->nt.members = prob->w->napsac_mem.p;
+        prob->nt.n = (uint32_t)n;
+        prob->nt.m = (uint32_t)m;
+        prob->nt.T = iterations;
         return GCR_OK;
     });
 }
@@ -4695,12 +4779,12 @@ static void load_rows(const double* correspondences, const uint32_t* idx, double
 
 // The host twin of a correspondence generator (k_generate_e / _g / _s), slot
 // by slot over `threads` host threads: attempts 0..100, the first success
-// wins.  An attempt draws M indices of n rows -- guided with gt, else uniform
-// -- and solve(idx, ms) returns its 0 .. NMODELS models.  inc_out / models_out
-// as gcr_debug_generate_h's.
+// wins.  An attempt draws M indices of n rows -- guided with gt, by NAPSAC with
+// nt, else uniform -- and solve(idx, ms) returns its 0 .. NMODELS models.
+// inc_out / models_out as gcr_debug_generate_h's.
 template <int M, int NMODELS, class Solve>
 static int host_generate(size_t n, const GuidedTable* gt, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
-                         uint8_t* inc_out, double* models_out, Solve solve) {
+                         uint8_t* inc_out, double* models_out, Solve solve, const NapsacTable* nt = nullptr) {
     threads = std::min(std::max(threads, 1), 256);
     return guard([&]() -> int {
         auto work = [&](uint32_t lo, uint32_t hi) {
@@ -4713,8 +4797,9 @@ static int host_generate(size_t n, const GuidedTable* gt, uint64_t seed, uint64_
                 for (; a < 101 && cnt == 0; ++a) {
                     uint32_t idx[M];
                     WordStream ws(seed, slot0 + s, a, kStreamMain, 0);
-                    const bool drawn = gt != nullptr ? sample_guided<M>(ws, *gt, gt->coarse, M, idx)
-                                                     : sample_distinct<M>(ws, n, M, idx);
+                    const bool drawn = nt != nullptr   ? sample_napsac<M>(ws, *nt, M, idx)
+                                       : gt != nullptr ? sample_guided<M>(ws, *gt, gt->coarse, M, idx)
+                                                       : sample_distinct<M>(ws, n, M, idx);
                     if (drawn) cnt = solve(idx, ms);
                 }
                 for (int q = 0; q < NMODELS; ++q) {
@@ -4856,6 +4941,11 @@ int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities
 int gcr_problem_set_prosac(gcr_problem* prob, uint64_t convergence_iterations) {
     if (!prob) return set_err(GCR_EINVAL, "null problem");
     return set_prosac(prob, convergence_iterations);
+}
+
+int gcr_problem_set_napsac(gcr_problem* prob, const double extent[4], uint64_t local_iterations) {
+    if (!prob) return set_err(GCR_EINVAL, "null problem");
+    return set_napsac(prob, extent, local_iterations);
 }
 
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
@@ -5392,7 +5482,7 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
         prob->w->gmodels.ensure(nh);
         hipStream_t s = prob->ctx->stream;
         HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s,
-                                 prob->guided(), prob->grav(), prob->sift(), prob->prosac()));
+                                 prob->guided(), prob->grav(), prob->sift(), prob->prosac(), prob->napsac()));
         HIPC(hipMemcpyAsync(inc_out, prob->w->inc.p, nh, hipMemcpyDeviceToHost, s));
         HIPC(hipMemcpyAsync(H_out, prob->w->gmodels.p, nh * sizeof(GeoModel), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
@@ -5413,7 +5503,7 @@ int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_
         out.ensure(std::max<size_t>(cnt, 1));
         hipStream_t s = prob->ctx->stream;
         HIPC(launch_debug_sample(prob->solver, prob->dp, seed, slot0, nslots, attempt, out.p, s, prob->guided(),
-                                 prob->prosac()));
+                                 prob->prosac(), prob->napsac()));
         HIPC(hipMemcpyAsync(idx_out, out.p, cnt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
         HIPC(hipStreamSynchronize(s));
         return GCR_OK;
@@ -5434,12 +5524,12 @@ int gcr_measure_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uin
         hipStream_t s = prob->ctx->stream;
         // one untimed launch first (code object load, caches)
         HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0, nslots, prob->w->inc.p, prob->w->gmodels.p, s,
-                                 prob->guided(), prob->grav(), prob->sift(), prob->prosac()));
+                                 prob->guided(), prob->grav(), prob->sift(), prob->prosac(), prob->napsac()));
         HIPC(hipEventRecord(prob->ctx->ev0, s));
         for (int r = 0; r < reps; ++r)
             HIPC(launch_generate_geo(prob->solver, prob->dp, seed, slot0 + (uint64_t)r * nslots, nslots, prob->w->inc.p,
                                      prob->w->gmodels.p, s, prob->guided(), prob->grav(), prob->sift(),
-                                     prob->prosac()));
+                                     prob->prosac(), prob->napsac()));
         HIPC(hipEventRecord(prob->ctx->ev1, s));
         HIPC(hipEventSynchronize(prob->ctx->ev1));
         float ms = 0.f;
@@ -5950,6 +6040,159 @@ int gcr_host_sample_prosac(uint64_t seed, uint64_t index, uint32_t sub, size_t n
         return sample_prosac<32>(ws, n, (int)m, pool, out) ? GCR_OK
                                                            : set_err(GCR_EINTERNAL, "sample budget exhausted");
     });
+}
+
+// ---- NAPSAC sampling (napsac.h): the host definition ------------------------
+static int check_napsac_args(const double* rows, size_t n, uint32_t m, const double* extent, uint64_t iterations) {
+    if (!rows || !extent) return set_err(GCR_EINVAL, "null argument");
+    if (m == 0 || m > 32 || n < m || n >= 0xffffffffull || iterations == 0 || iterations > kNapsacMaxIterations)
+        return set_err(GCR_EINVAL, "NAPSAC: need 1 <= m <= 32, m <= n < 2^32 - 1 and 1 <= local_iterations <= 2^40");
+    if (!napsac_extent_ok(extent))
+        return set_err(GCR_EINVAL, "NAPSAC: the extents {w1, h1, w2, h2} must be positive and finite");
+    return GCR_OK;
+}
+
+// the layers of n rows (x1, y1, x2, y2)
+static void host_napsac_layers(const double* rows, size_t n, const double* extent, NapsacLayers& layers) {
+    std::vector<double> col[4];
+    for (int d = 0; d < 4; ++d) {
+        col[d].resize(n);
+        for (size_t i = 0; i < n; ++i) col[d][i] = rows[4 * i + d];
+    }
+    const double* cols[4] = {col[0].data(), col[1].data(), col[2].data(), col[3].data()};
+    napsac_layers(cols, n, extent, layers);
+}
+
+int gcr_host_napsac_layers(const double* rows, size_t n, const double extent[4], uint32_t* members_out,
+                           uint32_t* start_out, uint32_t* count_out, uint32_t* pos_out) {
+    if (!members_out || !start_out || !count_out || !pos_out) return set_err(GCR_EINVAL, "null output pointer");
+    if (int e = check_napsac_args(rows, n, 1, extent, 1)) return e;
+    return guard([&]() -> int {
+        NapsacLayers layers;
+        host_napsac_layers(rows, n, extent, layers);
+        std::memcpy(members_out, layers.members.data(), layers.members.size() * sizeof(uint32_t));
+        for (int l = 0; l < kNapsacLayers; ++l)
+            for (size_t i = 0; i < n; ++i) {
+                start_out[l * n + i] = layers.rec[i].start[l];
+                count_out[l * n + i] = layers.rec[i].count[l];
+                pos_out[l * n + i] = layers.rec[i].pos[l];
+            }
+        return GCR_OK;
+    });
+}
+
+int gcr_host_sample_napsac(uint64_t seed, uint64_t index, uint32_t sub, const double* rows, size_t n, uint32_t m,
+                           const double extent[4], uint64_t local_iterations, uint32_t* out) {
+    if (!out) return set_err(GCR_EINVAL, "null output pointer");
+    if (int e = check_napsac_args(rows, n, m, extent, local_iterations)) return e;
+    return guard([&]() -> int {
+        NapsacLayers layers;
+        host_napsac_layers(rows, n, extent, layers);
+        const NapsacTable t = napsac_host_table(layers, n, m, local_iterations);
+        WordStream ws(seed, index, sub, kStreamMain, 0);
+        return sample_napsac<32>(ws, t, (int)m, out) ? GCR_OK : set_err(GCR_EINTERNAL, "sample budget exhausted");
+    });
+}
+
+int gcr_host_samples_napsac(uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t sub, const double* rows, size_t n,
+                            uint32_t m, const double extent[4], uint64_t local_iterations, uint32_t* out) {
+    if (!out) return set_err(GCR_EINVAL, "null output pointer");
+    if (int e = check_napsac_args(rows, n, m, extent, local_iterations)) return e;
+    return guard([&]() -> int {
+        NapsacLayers layers;
+        host_napsac_layers(rows, n, extent, layers);
+        const NapsacTable t = napsac_host_table(layers, n, m, local_iterations);
+        for (uint32_t s = 0; s < nslots; ++s) {
+            WordStream ws(seed, slot0 + s, sub, kStreamMain, 0);
+            uint32_t idx[32];
+            const bool ok = sample_napsac<32>(ws, t, (int)m, idx);
+            for (uint32_t j = 0; j < m; ++j) out[(size_t)m * s + j] = ok ? idx[j] : 0xffffffffu;
+        }
+        return GCR_OK;
+    });
+}
+
+int gcr_host_generate_napsac(int solver, const double* correspondences, const double* pixels, const double* sift,
+                             const double* G1, const double* G2, size_t n, const double extent[4],
+                             uint64_t local_iterations, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
+                             uint8_t* inc_out, double* models_out) {
+    if (!correspondences || !inc_out || !models_out) return set_err(GCR_EINVAL, "null argument");
+    const SolverRow row = solver_row(solver);
+    if (!row.corr) return set_err(GCR_EINVAL, "gcr_host_generate_napsac: correspondence solvers only");
+    if (row.needs_sift != (sift != nullptr) || row.needs_gravity != (G1 != nullptr && G2 != nullptr))
+        return set_err(GCR_EINVAL, "gcr_host_generate_napsac: SIFT columns / gravity rotations for the solver that "
+                                   "takes them, NULL for the others");
+    const double* grid_rows = pixels != nullptr ? pixels : correspondences;
+    if (int e = check_napsac_args(grid_rows, n, (uint32_t)row.m, extent, local_iterations)) return e;
+    GravRot rot;
+    if (row.needs_gravity && !load_rot(G1, G2, rot)) return GCR_EINVAL;
+    if (row.needs_sift)
+        if (int e = check_sift(sift, n)) return e;
+    NapsacLayers layers;
+    NapsacTable t;
+    if (int e = guard([&]() -> int {
+            host_napsac_layers(grid_rows, n, extent, layers);
+            t = napsac_host_table(layers, n, (uint32_t)row.m, local_iterations);
+            return GCR_OK;
+        }))
+        return e;
+    auto run = [&](auto mtag, auto ptag, auto solve) {
+        return host_generate<decltype(mtag)::value, decltype(ptag)::value>(n, nullptr, seed, slot0, nslots, threads,
+                                                                           inc_out, models_out, solve, &t);
+    };
+    switch (solver) {
+        case GCR_SOLVER_HOMOGRAPHY4: {
+            constexpr SolverRow r = kSolverTable[GCR_SOLVER_HOMOGRAPHY4];
+            return run(std::integral_constant<int, r.m>{}, std::integral_constant<int, r.per>{},
+                       [&](const uint32_t* idx, GeoModel* ms) {
+                           double x1[r.m], y1[r.m], x2[r.m], y2[r.m];
+                           load_rows<r.m>(correspondences, idx, x1, y1, x2, y2);
+                           return valid_sample_h4(x1, y1, x2, y2) && solve_h4(x1, y1, x2, y2, ms[0]) ? 1 : 0;
+                       });
+        }
+        case GCR_SOLVER_FUNDAMENTAL7: {
+            constexpr SolverRow r = kSolverTable[GCR_SOLVER_FUNDAMENTAL7];
+            return run(std::integral_constant<int, r.m>{}, std::integral_constant<int, r.per>{},
+                       [&](const uint32_t* idx, GeoModel* ms) {
+                           double x1[r.m], y1[r.m], x2[r.m], y2[r.m];
+                           load_rows<r.m>(correspondences, idx, x1, y1, x2, y2);
+                           F7Basis b;
+                           if (solve_f7_basis(x1, y1, x2, y2, b) == 0) return 0;
+                           int k = 0;
+                           for (int q = 0; q < 3; ++q)
+                               if (b.valid & (1u << q)) f7_model(b, f7_root(b, q), ms[k++].h);
+                           return k;
+                       });
+        }
+        case GCR_SOLVER_ESSENTIAL5: {
+            constexpr SolverRow r = kSolverTable[GCR_SOLVER_ESSENTIAL5];
+            return run(std::integral_constant<int, r.m>{}, std::integral_constant<int, r.per>{},
+                       [&](const uint32_t* idx, GeoModel* ms) {
+                           double x1[r.m], y1[r.m], x2[r.m], y2[r.m];
+                           load_rows<r.m>(correspondences, idx, x1, y1, x2, y2);
+                           return solve_e5(x1, y1, x2, y2, ms);
+                       });
+        }
+        case GCR_SOLVER_ESSENTIAL3_GRAVITY: {
+            constexpr SolverRow r = kSolverTable[GCR_SOLVER_ESSENTIAL3_GRAVITY];
+            return run(std::integral_constant<int, r.m>{}, std::integral_constant<int, r.per>{},
+                       [&](const uint32_t* idx, GeoModel* ms) {
+                           double x1[r.m], y1[r.m], x2[r.m], y2[r.m];
+                           load_rows<r.m>(correspondences, idx, x1, y1, x2, y2);
+                           return solve_g3(x1, y1, x2, y2, rot, ms);
+                       });
+        }
+        default: {
+            constexpr SolverRow r = kSolverTable[GCR_SOLVER_HOMOGRAPHY2_SIFT];
+            return run(std::integral_constant<int, r.m>{}, std::integral_constant<int, r.per>{},
+                       [&](const uint32_t* idx, GeoModel* ms) {
+                           double x1[2], y1[2], x2[2], y2[2];
+                           SiftPair sp;
+                           load_sift_sample(correspondences, sift, idx, x1, y1, x2, y2, sp);
+                           return solve_s2(x1, y1, x2, y2, sp, ms);
+                       });
+        }
+    }
 }
 
 int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m) {

@@ -65,15 +65,11 @@ inline uint64_t grid_axis_index(double v) {
     return (uint64_t)(int64_t)f;
 }
 
-// coords: `dims` column pointers of n values each; the explicit edge list
-// (u, v) only when `with_edges` (the engine needs the cells alone)
-inline void grid_edges(const double* const* coords, int dims, size_t n, const double* cell_size,
-                       uint64_t cell_number, NeighbourEdges& out, bool with_edges = true) {
-    out.u.clear();
-    out.v.clear();
-    out.off.assign(1, 0);
-    out.nodes.clear();
-    // (cell key, point) sorted: cells in key order, points ascending inside
+// The grid's grouping: (cell key, point) of n points sorted, cells in key
+// order, points ascending inside a cell.  coords: `dims` column pointers of n
+// values each.  (grid_edges' cells, and napsac_layers.h's.)
+inline std::vector<std::pair<uint64_t, uint32_t>> grid_sorted_cells(const double* const* coords, int dims, size_t n,
+                                                                    const double* cell_size, uint64_t cell_number) {
     std::vector<std::pair<uint64_t, uint32_t>> kp(n);
     uint64_t kmax = 0;
     for (size_t i = 0; i < n; ++i) {
@@ -97,6 +93,18 @@ inline void grid_edges(const double* const* coords, int dims, size_t n, const do
     } else {
         std::sort(kp.begin(), kp.end());
     }
+    return kp;
+}
+
+// coords: `dims` column pointers of n values each; the explicit edge list
+// (u, v) only when `with_edges` (the engine needs the cells alone)
+inline void grid_edges(const double* const* coords, int dims, size_t n, const double* cell_size,
+                       uint64_t cell_number, NeighbourEdges& out, bool with_edges = true) {
+    out.u.clear();
+    out.v.clear();
+    out.off.assign(1, 0);
+    out.nodes.clear();
+    const std::vector<std::pair<uint64_t, uint32_t>> kp = grid_sorted_cells(coords, dims, n, cell_size, cell_number);
     std::vector<uint8_t> in_cell(n, 0);
     for (size_t s0 = 0; s0 < n;) {
         size_t e = s0;

@@ -9,6 +9,7 @@
 #include "geo.h"
 #include "gram.h"
 #include "guided.h"
+#include "napsac.h"
 #include "prosac.h"
 #include "rect.h"
 #include "solver.h"
@@ -297,18 +298,24 @@ bool verify_chains(uint32_t nslots);
 // (prosac.h) by the generators' PROSAC instantiations; slot0 and lanes of the
 // table are filled by the launch.  A launch whose first slot is past g[N]
 // launches the uniform kernel.
+// napsac != nullptr (guided and prosac must then be nullptr): samples from the
+// neighbourhood of their first row (napsac.h) by the generators' NAPSAC
+// instantiations.  A launch whose first slot is past T launches the uniform
+// kernel.
 // grav: the two gravity rotations (grav.h), sift: the device pointers of the
 // stored SIFT columns (sifth.h) -- each required by the solver whose row has
 // needs_gravity / needs_sift and nullptr for the others.
 hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
                                uint8_t* inc, GeoModel* models, hipStream_t stream,
                                const GuidedTable* guided = nullptr, const GravRot* grav = nullptr,
-                               const SiftCols* sift = nullptr, const ProsacTable* prosac = nullptr);
+                               const SiftCols* sift = nullptr, const ProsacTable* prosac = nullptr,
+                               const NapsacTable* napsac = nullptr);
 // The generators' sampling function alone (tests): the solver's m indices of
 // attempt `attempt` of each slot into out, all-ones where the draw budget ran out.
 hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
                                uint32_t attempt, uint32_t* out, hipStream_t stream,
-                               const GuidedTable* guided = nullptr, const ProsacTable* prosac = nullptr);
+                               const GuidedTable* guided = nullptr, const ProsacTable* prosac = nullptr,
+                               const NapsacTable* napsac = nullptr);
 // Hypotheses per workgroup of the batch scorers at a launch of nh (64, 16 or
 // 4; GCR_SPLIT_H pins one for sweeps).
 int split_h(uint32_t nh);

@@ -18,6 +18,7 @@
 #include "fm_groups.h"
 #include "grav.h"
 #include "guided.h"
+#include "napsac.h"
 #include "philox.h"
 #include "prosac.h"
 #include "prosac_stop.h"
@@ -43,9 +44,11 @@ constexpr int kMaskBlock = 256;
 // ------------------------------------------------------------- generate ----
 // How the correspondence estimators' attempts draw their sample: uniformly
 // (philox.h sample_distinct), guided by the problem's probabilities
-// (guided.h), the coarse table read from the workgroup's LDS copy, or by
+// (guided.h), the coarse table read from the workgroup's LDS copy, by
 // PROSAC's growing pool (prosac.h), the slot's pool size searched in the
-// workgroup's LDS window of the growth table.
+// workgroup's LDS window of the growth table, or from the neighbourhood of the
+// sample's first row (napsac.h), the row's record and its cell's members read
+// from global memory.
 struct UniformDraw {};
 struct GuidedDraw {
     GuidedTable t;
@@ -56,6 +59,9 @@ struct ProsacDraw {
     uint32_t n_lo;
     uint32_t n;                         // N
     uint64_t g_n;                       // g[N]
+};
+struct NapsacDraw {
+    NapsacTable t;
 };
 
 template <int M, class DRAW>
@@ -70,6 +76,8 @@ GCR_DEVICE bool draw_sample(WordStream& ws, uint64_t n, const DRAW& d, uint32_t*
             pool = i < d.n - d.n_lo ? d.n_lo + i : d.n;     // (a slot of this workgroup never needs the clamp)
         }
         return sample_prosac<M>(ws, d.n, M, pool, idx);
+    } else if constexpr (std::is_same_v<DRAW, NapsacDraw>) {
+        return sample_napsac<M>(ws, d.t, M, idx);
     } else {
         return sample_distinct<M>(ws, n, M, idx);
     }
@@ -106,6 +114,8 @@ GCR_DEVICE ProsacDraw stage_draw(const ProsacTable& t) {
     __syncthreads();
     return ProsacDraw{s_win, n_lo, t.n, t.g_n};
 }
+// NAPSAC stages nothing: a row's record is one cache line wherever i0 falls
+GCR_DEVICE NapsacDraw stage_draw(const NapsacTable& t) { return NapsacDraw{t}; }
 
 // One attempt of one outer-iteration slot: Philox sample -> sample validity ->
 // minimal solve.  Attempts of a slot are independent draws (the counter RNG is
@@ -5470,6 +5480,14 @@ bool prosac_table_fits(const ProsacTable* prosac, const GuidedTable* guided, con
                                  prosac->m == (uint32_t)m && prosac->n >= prosac->m && prosac->g_n >= 1);
 }
 
+// the NAPSAC table of this problem and solver, never together with another one
+bool napsac_table_fits(const NapsacTable* napsac, const GuidedTable* guided, const ProsacTable* prosac,
+                       const DevProblem& p, int m) {
+    return napsac == nullptr || (guided == nullptr && prosac == nullptr && napsac->rec != nullptr &&
+                                 napsac->members != nullptr && napsac->n == p.cls[0].n && napsac->m == (uint32_t)m &&
+                                 napsac->n >= napsac->m && napsac->T >= 1 && napsac->T <= kNapsacMaxIterations);
+}
+
 bool guided_table_fits(const GuidedTable* guided, const DevProblem& p) {
     return guided == nullptr || (guided->n == p.cls[0].n && guided->buckets <= kGuidedCoarse && guided->buckets != 0 &&
                                  (size_t)guided->stride * guided->buckets >= guided->n);
@@ -5520,15 +5538,19 @@ int gen_lanes(int solver, uint32_t nslots) {
 
 hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
                                uint8_t* inc, GeoModel* models, hipStream_t stream, const GuidedTable* guided,
-                               const GravRot* grav, const SiftCols* sift, const ProsacTable* prosac) {
+                               const GravRot* grav, const SiftCols* sift, const ProsacTable* prosac,
+                               const NapsacTable* napsac) {
     if (nslots == 0) return hipSuccess;
     const SolverRow row = solver_row(solver);
     if (!row.corr || row.kind != p.kind) return hipErrorInvalidValue;
     if (row.needs_gravity != (grav != nullptr)) return hipErrorInvalidValue;
     if (row.needs_sift != (sift != nullptr)) return hipErrorInvalidValue;
-    if (!guided_table_fits(guided, p) || !prosac_table_fits(prosac, guided, p, row.m)) return hipErrorInvalidValue;
-    // a launch that starts past g[N] is the uniform kernel itself, no table
+    if (!guided_table_fits(guided, p) || !prosac_table_fits(prosac, guided, p, row.m) ||
+        !napsac_table_fits(napsac, guided, prosac, p, row.m))
+        return hipErrorInvalidValue;
+    // a launch that starts past g[N] (NAPSAC: past T) is the uniform kernel itself, no table
     if (prosac != nullptr && slot0 >= prosac->g_n) prosac = nullptr;
+    if (napsac != nullptr && slot0 >= napsac->T) napsac = nullptr;
     // GCR_GEN_WIDEN=0: the fundamental-matrix generator keeps fixed groups of
     // G lanes per slot (k_generate_f) instead of widening them (k_generate_fw).
     // Both knobs are read per launch (tests switch them in-process).
@@ -5540,7 +5562,7 @@ hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, u
     auto go = [&](auto gtag) {
         constexpr int G = decltype(gtag)::value;
         const dim3 grid(blocks_for((size_t)nslots * G, kGenBlock)), block(kGenBlock);
-        // t: nothing (the uniform kernels), the guided table or the PROSAC table
+        // t: nothing (the uniform kernels), the guided, the PROSAC or the NAPSAC table
         auto run = [&](auto... t) {
             with_corr_solver(solver, [&](auto stag) {
                 constexpr int S = decltype(stag)::value;
@@ -5576,6 +5598,8 @@ hipError_t launch_generate_geo(int solver, const DevProblem& p, uint64_t seed, u
             pt.slot0 = slot0;
             pt.lanes = (uint32_t)G;
             run(pt);
+        } else if (napsac != nullptr) {
+            run(*napsac);
         } else {
             run();
         }
@@ -5615,12 +5639,14 @@ __global__ __launch_bounds__(kGenBlock) void k_debug_sample(uint32_t n, uint64_t
 
 hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, uint64_t slot0, uint32_t nslots,
                                uint32_t attempt, uint32_t* out, hipStream_t stream, const GuidedTable* guided,
-                               const ProsacTable* prosac) {
+                               const ProsacTable* prosac, const NapsacTable* napsac) {
     if (nslots == 0) return hipSuccess;
     if (!solver_row(solver).corr) return hipErrorInvalidValue;
-    if (!guided_table_fits(guided, p) || !prosac_table_fits(prosac, guided, p, solver_row(solver).m))
+    if (!guided_table_fits(guided, p) || !prosac_table_fits(prosac, guided, p, solver_row(solver).m) ||
+        !napsac_table_fits(napsac, guided, prosac, p, solver_row(solver).m))
         return hipErrorInvalidValue;
     if (prosac != nullptr && slot0 >= prosac->g_n) prosac = nullptr;
+    if (napsac != nullptr && slot0 >= napsac->T) napsac = nullptr;
     const dim3 grid(blocks_for(nslots, kGenBlock)), block(kGenBlock);
     auto run = [&](auto... t) {
         with_corr_solver(solver, [&](auto stag) {
@@ -5636,6 +5662,8 @@ hipError_t launch_debug_sample(int solver, const DevProblem& p, uint64_t seed, u
         pt.slot0 = slot0;
         pt.lanes = 1;
         run(pt);
+    } else if (napsac != nullptr) {
+        run(*napsac);
     } else {
         run();
     }

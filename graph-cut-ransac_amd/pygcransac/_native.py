@@ -229,6 +229,15 @@ def _load():
     L.gcr_host_prosac_stop.argtypes = [u8p, C.c_size_t, C.c_uint32, u32p, dp, u32p, u32p]
     L.gcr_host_prosac_stop_number.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_double, u64p]
     L.gcr_debug_prosac_stop_h.argtypes = [vp, C.POINTER(Params), dp, C.c_uint32, u32p, u32p, u32p]
+    # NAPSAC sampling (csrc/napsac.h): gcr_problem_set_napsac and its host definition
+    L.gcr_problem_set_napsac.argtypes = [vp, dp, C.c_uint64]
+    L.gcr_host_napsac_layers.argtypes = [dp, C.c_size_t, dp, u32p, u32p, u32p, u32p]
+    L.gcr_host_sample_napsac.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, dp, C.c_size_t, C.c_uint32, dp,
+                                         C.c_uint64, u32p]
+    L.gcr_host_samples_napsac.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, dp, C.c_size_t, C.c_uint32,
+                                          dp, C.c_uint64, u32p]
+    L.gcr_host_generate_napsac.argtypes = [C.c_int, dp, dp, dp, dp, dp, C.c_size_t, dp, C.c_uint64, C.c_uint64,
+                                           C.c_uint64, C.c_uint32, C.c_int, C.POINTER(C.c_uint8), dp]
     # essential matrix (csrc/ess.h): pixel rows + calibration matrices
     L.gcr_find_essential_matrix.argtypes = [vp, vp, C.c_size_t, vp, vp, vp, C.POINTER(Params), vp, vp,
                                             C.POINTER(Stats)]

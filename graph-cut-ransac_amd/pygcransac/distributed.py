@@ -236,7 +236,7 @@ class Comm:
 def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None, rank: int = 0, world: int = 1,
                         dist=None, device: Optional[int] = None, coll_device=None, comm: Optional[Comm] = None,
                         probabilities=None, K1=None, K2=None, G1=None, G2=None, sift=None,
-                        prosac_convergence: Optional[int] = None):
+                        prosac_convergence: Optional[int] = None, napsac=None):
     """One estimator problem over `world` ranks.
 
     Every rank calls this with the same inputs; each verifies its block of
@@ -260,6 +260,11 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
     ``params={"flags": _native.FLAG_PROSAC_STOP, ...}`` stops the run on
     PROSAC's own bound (csrc/prosac_stop.h; every rank computes the chain
     members' prefixes itself, as for the mass).
+    `napsac` = (extent, iterations) (correspondence solvers; exclusive with
+    the other two) switches it to NAPSAC sampling (gcr_problem_set_napsac,
+    csrc/napsac.h): extent = (w1, h1, w2, h2) and the local length, the same on
+    every rank.  A slot's sample is a function of (seed, slot, attempt) alone,
+    so the sharded run stays bit-identical to the single-rank one.
     Solver 5 (essential matrix) takes pixel rows and the calibration matrices
     `K1`, `K2` (3 x 3); its threshold is in pixels and H is E in normalised
     coordinates.  Solver 6 (essential matrix with known gravity) takes the
@@ -307,6 +312,9 @@ def run_problem_sharded(solver: int, f0, f1=None, params: Optional[dict] = None,
             N.check(N.lib.gcr_problem_set_probabilities(h, w.ctypes.data, w.shape[0]))
         if prosac_convergence is not None:
             N.check(N.lib.gcr_problem_set_prosac(h, int(prosac_convergence)))
+        if napsac is not None:
+            extent, iterations = napsac
+            N.check(N.lib.gcr_problem_set_napsac(h, (C.c_double * 4)(*[float(v) for v in extent]), int(iterations)))
         p = N.default_params()
         for k, v in (params or {}).items():
             setattr(p, k, v)

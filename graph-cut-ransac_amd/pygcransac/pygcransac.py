@@ -476,19 +476,44 @@ def _as_convergence(prosac_convergence):
     return t
 
 
+NAPSAC_MAX_ITERATIONS = 1 << 40
+
+
+def _as_napsac_iterations(napsac_iterations, n):
+    """NAPSAC's local length T: None is ceil(n / 2), upstream's sampler_length
+    0.5 x N."""
+    if napsac_iterations is None:
+        return max(1, (n + 1) // 2)
+    t = _as_size_t(napsac_iterations, "napsac_iterations")
+    if t < 1 or t > NAPSAC_MAX_ITERATIONS:
+        raise ValueError(f"napsac_iterations must be in 1 .. 2^40, got {napsac_iterations}.")
+    return t
+
+
+def napsac_extent(correspondences, h1, w1, h2, w2):
+    """The extents {w1, h1, w2, h2} NAPSAC's grid layers divide: the image
+    sizes, an unknown one (<= 0) taken from the data by grid_cell_sizes' rule."""
+    return grid_cell_sizes(correspondences, h1, w1, h2, w2, 1)
+
+
 def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, probabilities, threshold, conf,
                          spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                          batch_slots, return_stats, min_rows, neighborhood_size, guided_stop=False, min_weights=None,
-                         create=None, prosac_convergence=100000, prosac_stop=False):
+                         create=None, prosac_convergence=100000, prosac_stop=False, napsac_iterations=None):
     """min_weights: the minimal sample size the probabilities are checked for
     (default: min_rows).  create(ctx, rows, order, out): a resident problem of
-    the estimator over `rows`, the caller's rows taken in `order` (sampler=1)."""
+    the estimator over `rows`, the caller's rows taken in `order` (sampler=1;
+    sampler=2: every row in place)."""
     for name, v in (("h1", h1), ("w1", w1), ("h2", h2), ("w2", w2)):
         _as_double(v, name)
     sampler_id = _as_size_t(sampler, "sampler")
-    if sampler_id not in (0, 1, 3):
-        raise ValueError(f"Unsupported sampler {sampler}: only 0 (uniform), 1 (PROSAC, ordered by quality scores) "
-                         f"and 3 (guided by probabilities, importance sampling) are supported.")
+    if sampler_id not in (0, 1, 2, 3):
+        raise ValueError(f"Unsupported sampler {sampler}: only 0 (uniform), 1 (PROSAC, ordered by quality scores), "
+                         f"2 (NAPSAC, local by position) and 3 (guided by probabilities, importance sampling) are "
+                         f"supported.")
+    if sampler_id == 2 and probabilities is not None and len(probabilities) != 0:
+        raise ValueError("Unsupported sampler 2 with probabilities: NAPSAC samples by position and takes none "
+                         "(PROSAC is 1, guided sampling 3).")
     if sampler_id == 0 and probabilities is not None and len(probabilities) != 0:
         raise ValueError("The uniform sampler (0) takes no probabilities; they must be empty (sampler=3 uses them).")
     if sampler_id == 3 and probabilities is None:
@@ -523,6 +548,9 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
     if sampler_id == 1:
         convergence = _as_convergence(prosac_convergence)
         order = prosac_order(_as_scores(probabilities, n))
+    if sampler_id == 2:
+        local = _as_napsac_iterations(napsac_iterations, n)
+        extent = (C.c_double * 4)(*napsac_extent(f, h1, w1, h2, w2))
     ctx = N.context(device)
     if sampler_id == 1:
         # the resident-problem API on the rows in quality order; the mask goes
@@ -538,6 +566,16 @@ def _correspondence_call(entry, guided_entry, correspondences, h1, w1, h2, w2, p
         finally:
             N.lib.gcr_problem_destroy(h)
         mask[order] = ordered
+    elif sampler_id == 2:
+        # the resident-problem API on the rows as they are
+        h = C.c_void_p()
+        N.check(create(ctx, f, np.arange(n), C.byref(h)))
+        try:
+            N.check(N.lib.gcr_problem_set_napsac(h, extent, local))
+            rc = N.lib.gcr_problem_run(h, C.byref(p), mask.ctypes.data_as(C.POINTER(C.c_uint8)), None,
+                                       M.ctypes.data_as(C.POINTER(C.c_double)), C.byref(N.RectModel()), C.byref(st))
+        finally:
+            N.lib.gcr_problem_destroy(h)
     elif sampler_id == 3:
         rc = guided_entry(ctx, f.ctypes.data, n, w.ctypes.data, C.byref(p), mask.ctypes.data, M.ctypes.data,
                           C.byref(st))
@@ -561,7 +599,7 @@ def _plain_create(solver):
 def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                    spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                    neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False, guided_stop=False,
-                   prosac_convergence=100000, prosac_stop=False):
+                   prosac_convergence=100000, prosac_stop=False, napsac_iterations=None):
     """4-point homography with graph-cut LO -- an EXTENSION (SURVEY.md §8(f)
     row 3): this fork has no homography estimator (finding 0.1); the argument
     names and order follow upstream pygcransac's findHomography.
@@ -599,7 +637,18 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     non-randomness / maximality stop (csrc/prosac_stop.h), the same bound on
     the best model's inlier share over the best-ranked prefix that is
     non-random and that the samples drawn so far cover; it can only end a run
-    sooner.  ``guided_stop`` does not apply.
+    sooner.  ``guided_stop`` does not apply.  ``sampler=2`` is (progressive)
+    NAPSAC (upstream's sampler 2; csrc/napsac.h is the definition): it takes
+    no ``probabilities``, only the positions.  During the first
+    ``napsac_iterations`` iterations (1 .. 2^40; None: half the number of
+    correspondences, upstream's length) a sample's first correspondence is
+    drawn uniformly and the others from its cell of a grid over (x1, y1, x2,
+    y2) -- 16, 8, 4, then 2 cells per axis over the image sizes, a quarter of
+    the length each, the next coarser grid where the cell is too small --
+    and from then on every iteration is the uniform sampler's.  It suits
+    inliers that are a local structure among outliers spread over the images.
+    The stop is the uniform bound, also during the local iterations, where
+    it is a heuristic; ``guided_stop`` and ``prosac_stop`` do not apply.  The other four correspondence estimators take it the same way.
     ``threshold`` is the inlier threshold in pixels
     of the second image (MSAC threshold 2.25 * threshold, as the rectification
     solvers).
@@ -611,13 +660,13 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
                                 min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
                                 create=_plain_create(N.SOLVER_HOMOGRAPHY4), prosac_convergence=prosac_convergence,
-                                prosac_stop=prosac_stop)
+                                prosac_stop=prosac_stop, napsac_iterations=napsac_iterations)
 
 
 def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                           spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50,
                           *, neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                          guided_stop=False, prosac_convergence=100000, prosac_stop=False):
+                          guided_stop=False, prosac_convergence=100000, prosac_stop=False, napsac_iterations=None):
     """7-point fundamental matrix with graph-cut LO -- an EXTENSION like
     findHomography (same arguments, the same neighbourhood grid; upstream
     pygcransac's findFundamentalMatrix order).  The residual is the Sampson distance in pixels; a sample yields up
@@ -635,7 +684,7 @@ def findFundamentalMatrix(correspondences, h1, w1, h2, w2, probabilities=None, t
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 7, neighborhood_size, guided_stop,
                                 create=_plain_create(N.SOLVER_FUNDAMENTAL7), prosac_convergence=prosac_convergence,
-                                prosac_stop=prosac_stop)
+                                prosac_stop=prosac_stop, napsac_iterations=napsac_iterations)
 
 
 def _as_calibration(K, name):
@@ -648,7 +697,7 @@ def _as_calibration(K, name):
 def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                         spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                         neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                        guided_stop=False, prosac_convergence=100000, prosac_stop=False):
+                        guided_stop=False, prosac_convergence=100000, prosac_stop=False, napsac_iterations=None):
     """5-point essential matrix with graph-cut LO for calibrated cameras -- an
     EXTENSION like findFundamentalMatrix (upstream pygcransac's
     findEssentialMatrix order; csrc/ess.h is the solver's definition).
@@ -686,7 +735,7 @@ def findEssentialMatrix(correspondences, K1, K2, h1, w1, h2, w2, probabilities=N
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                                 batch_slots, return_stats, 5, neighborhood_size, guided_stop, create=create,
                                 prosac_convergence=prosac_convergence,
-                                prosac_stop=prosac_stop)
+                                prosac_stop=prosac_stop, napsac_iterations=napsac_iterations)
 
 
 def _as_rotation(G, name):
@@ -700,7 +749,7 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
                                probabilities=None, threshold=1.0, conf=0.99, spatial_coherence_weight=0.975,
                                max_iters=10000, min_iters=50, sampler=0, lo_number=50, *, neighborhood_size=8, seed=0,
                                device=None, batch_slots=0, return_stats=False, guided_stop=False,
-                               prosac_convergence=100000, prosac_stop=False):
+                               prosac_convergence=100000, prosac_stop=False, napsac_iterations=None):
     """3-point essential matrix with graph-cut LO for calibrated cameras whose
     gravity direction is known (a phone, a vehicle, any IMU rig) -- an
     EXTENSION like findEssentialMatrix (upstream pygcransac's
@@ -746,13 +795,13 @@ def findGravityEssentialMatrix(correspondences, K1, K2, gravity_source, gravity_
                                 spatial_coherence_weight, max_iters, min_iters, sampler, lo_number, seed, device,
                                 batch_slots, return_stats, 3, neighborhood_size, guided_stop, create=create,
                                 prosac_convergence=prosac_convergence,
-                                prosac_stop=prosac_stop)
+                                prosac_stop=prosac_stop, napsac_iterations=napsac_iterations)
 
 
 def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, threshold=1.0, conf=0.99,
                        spatial_coherence_weight=0.975, max_iters=10000, min_iters=50, sampler=0, lo_number=50, *,
                        neighborhood_size=8, seed=0, device=None, batch_slots=0, return_stats=False,
-                       guided_stop=False, prosac_convergence=100000, prosac_stop=False):
+                       guided_stop=False, prosac_convergence=100000, prosac_stop=False, napsac_iterations=None):
     """Homography from TWO SIFT correspondences with graph-cut LO -- an
     EXTENSION like findHomography (what upstream pygcransac's findHomography
     runs with its SIFT-based solver).  Upstream's solver is not part of this
@@ -800,4 +849,4 @@ def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, thre
                                 threshold, conf, spatial_coherence_weight, max_iters, min_iters, sampler, lo_number,
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
                                 min_weights=2, create=create, prosac_convergence=prosac_convergence,
-                                prosac_stop=prosac_stop)
+                                prosac_stop=prosac_stop, napsac_iterations=napsac_iterations)

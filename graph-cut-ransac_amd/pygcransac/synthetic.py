@@ -129,6 +129,31 @@ def problem_h(n: int = 5_000, outlier_ratio: float = 0.5, seed: int = DEFAULT_SE
     return np.ascontiguousarray(corr[perm]), truth[perm], H.copy(), 2.0
 
 
+def problem_h_local(n: int = 5_000, outlier_ratio: float = 0.9, seed: int = DEFAULT_SEED, region: float = 0.25,
+                    noise: float = 0.5, H: np.ndarray = H_GT):
+    """problem_h with the inliers a local structure: their image-1 points lie
+    in a seeded `region` x `region` window of the image (fractions of its
+    width and height); the outliers stay uniform in both images.  The case
+    NAPSAC sampling (csrc/napsac.h) is for."""
+    rng = np.random.default_rng(seed)
+    n_out = int(round(n * outlier_ratio))
+    n_in = n - n_out
+    x0 = rng.uniform(0, IMG_W * (1.0 - region))
+    y0 = rng.uniform(0, IMG_H * (1.0 - region))
+    x1 = rng.uniform(x0, x0 + IMG_W * region, n_in)
+    y1 = rng.uniform(y0, y0 + IMG_H * region, n_in)
+    w = H[2, 0] * x1 + H[2, 1] * y1 + H[2, 2]
+    x2 = (H[0, 0] * x1 + H[0, 1] * y1 + H[0, 2]) / w + rng.normal(0, noise, n_in)
+    y2 = (H[1, 0] * x1 + H[1, 1] * y1 + H[1, 2]) / w + rng.normal(0, noise, n_in)
+    inl = np.stack([x1, y1, x2, y2], axis=1)
+    out = np.stack([rng.uniform(0, IMG_W, n_out), rng.uniform(0, IMG_H, n_out),
+                    rng.uniform(0, IMG_W, n_out), rng.uniform(0, IMG_H, n_out)], axis=1)
+    corr = np.concatenate([inl, out])
+    truth = np.concatenate([np.ones(n_in, bool), np.zeros(n_out, bool)])
+    perm = rng.permutation(n)
+    return np.ascontiguousarray(corr[perm]), truth[perm], H.copy(), 2.0
+
+
 def _rot(yaw, pitch, roll):
     cy, sy, cp, sp, cr, sr = (math.cos(yaw), math.sin(yaw), math.cos(pitch), math.sin(pitch), math.cos(roll),
                               math.sin(roll))

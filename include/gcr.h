@@ -45,7 +45,9 @@ extern "C" {
  * and so the one with known gravity (GCR_SOLVER_ESSENTIAL3_GRAVITY), the
  * host hook gcr_host_guided_index, and the homography from two SIFT
  * correspondences (GCR_SOLVER_HOMOGRAPHY2_SIFT).  PROSAC sampling and its
- * stop (GCR_FLAG_PROSAC_STOP) likewise: a new flag bit and new functions. */
+ * stop (GCR_FLAG_PROSAC_STOP) likewise: a new flag bit and new functions.
+ * NAPSAC sampling (gcr_problem_set_napsac and its host hooks): new functions
+ * only. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -364,6 +366,34 @@ int gcr_problem_set_probabilities(gcr_problem* prob, const double* probabilities
  * a PROSAC problem is GCR_EINVAL, as is GCR_FLAG_PROSAC_STOP on any other.
  * gcr_solve_batch's items stay uniform. */
 int gcr_problem_set_prosac(gcr_problem* prob, uint64_t convergence_iterations);
+/* NAPSAC sampling (upstream's sampler 2, progressive NAPSAC; csrc/napsac.h is
+ * the definition) for a resident correspondence problem of any of the five
+ * solvers.  It needs no scores, only the positions: a slot below
+ * `local_iterations` (T; 1 .. 2^40) draws its first row uniformly and the
+ * others from that row's cell of a grid over (x1, y1, x2, y2) -- 16, 8, 4,
+ * then 2 cells per axis in the four quarters of T, the next coarser layer
+ * where the cell holds fewer rows than a minimal sample -- and every slot
+ * from T on draws the uniform sampler's own sample.  `extent` = {w1, h1, w2,
+ * h2}, positive and finite: the image sizes the grids divide (an unknown size:
+ * the data's extent, as pygcransac.grid_cell_sizes computes it).  The layers
+ * are built on the host from the problem's pixel columns and uploaded; a
+ * slot's sample is a function of (seed, slot, attempt) alone, so runs stay
+ * bit-identical across batch_slots, shards and ranks.  Everything that
+ * generates from the problem afterwards -- gcr_problem_run, _run_sharded,
+ * _run_comm, _verify_batch(es), gcr_debug_generate_h, gcr_debug_sample_h,
+ * gcr_measure_generate_h -- uses it; local optimisation's inner sampler stays
+ * uniform and the stop is the uniform bound: what it describes from slot T on,
+ * and applied before T too, where it is a heuristic (a run whose bound falls
+ * below T ends inside the local phase).  local_iterations == 0 returns
+ * the problem to uniform sampling (extent is then not read).  Either call
+ * first waits for a speculative chunk a previous run left in flight.
+ * GCR_EINVAL, the problem left as it was: rectification problems, bad extents,
+ * local_iterations > 2^40, a problem with probabilities or PROSAC set (the
+ * three samplers are exclusive: clear one first; likewise
+ * gcr_problem_set_probabilities and gcr_problem_set_prosac on a NAPSAC
+ * problem).  GCR_FLAG_GUIDED_STOP or GCR_FLAG_PROSAC_STOP on a NAPSAC problem
+ * is GCR_EINVAL.  gcr_solve_batch's items stay uniform. */
+int gcr_problem_set_napsac(gcr_problem* prob, const double extent[4], uint64_t local_iterations);
 /* full estimator call on the resident problem (same semantics as gcr_rect_*) */
 int gcr_problem_run(gcr_problem* prob, const gcr_params* params, uint8_t* mask0_out, uint8_t* mask1_out,
                     double* H_out, gcr_rect_model* model_out, gcr_stats* stats_out);
@@ -484,7 +514,7 @@ int gcr_debug_generate_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint3
  * as many per slot,
  * all-ones where the draw budget ran out), with the problem's sampler --
  * guided after gcr_problem_set_probabilities, PROSAC after
- * gcr_problem_set_prosac, else uniform */
+ * gcr_problem_set_prosac, NAPSAC after gcr_problem_set_napsac, else uniform */
 int gcr_debug_sample_h(gcr_problem* prob, uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t attempt,
                        uint32_t* idx_out);
 /* measurement (tools/guided_bench.py): HIP-event time per launch, in ms, of
@@ -637,6 +667,32 @@ int gcr_host_prosac_stop(const uint8_t* mask, size_t n, uint32_t m, const uint32
  * of m at `confidence` (UINT64_MAX where the reference's guard returns it).
  * best_n == 0 or best_i > best_n: GCR_EINVAL */
 int gcr_host_prosac_stop_number(uint32_t best_i, uint32_t best_n, uint32_t m, double confidence, uint64_t* out);
+/* host-only: NAPSAC's layers (csrc/napsac.h) of n rows (x1, y1, x2, y2) over
+ * extent {w1, h1, w2, h2}: members_out[l * n ..] is grid layer l's member list
+ * (l = 0..3: 16, 8, 4, 2 cells per axis; cells in key order, rows ascending
+ * inside), start / count / pos_out[l * n + i] row i's cell in that layer */
+int gcr_host_napsac_layers(const double* rows, size_t n, const double extent[4], uint32_t* members_out,
+                           uint32_t* start_out, uint32_t* count_out, uint32_t* pos_out);
+/* host-only: one NAPSAC sample, the generators' function: attempt `sub` of
+ * slot `index` (main stream, class 0) with local length 1 .. 2^40, m <= 32
+ * indices in out; gcr_host_samples_napsac: attempt `sub` of nslots slots from
+ * slot0 over one set of layers (out: m per slot, all-ones where the draw
+ * budget ran out) */
+int gcr_host_sample_napsac(uint64_t seed, uint64_t index, uint32_t sub, const double* rows, size_t n, uint32_t m,
+                           const double extent[4], uint64_t local_iterations, uint32_t* out);
+int gcr_host_samples_napsac(uint64_t seed, uint64_t slot0, uint32_t nslots, uint32_t sub, const double* rows, size_t n,
+                            uint32_t m, const double extent[4], uint64_t local_iterations, uint32_t* out);
+/* host-only: the host twin of a correspondence generator under NAPSAC
+ * sampling, for all five solvers (gcr_host_generate_e / _g / _s with the
+ * NAPSAC sampler, and the same for the 4-point homography and the 7-point
+ * fundamental matrix).  correspondences: the rows the solver reads (K-normalised
+ * for the essential solvers); pixels: the rows the layers lie over (NULL: the
+ * correspondences themselves); sift, G1 / G2: for the solver that takes them,
+ * NULL for the others.  inc_out / models_out as gcr_debug_generate_h's. */
+int gcr_host_generate_napsac(int solver, const double* correspondences, const double* pixels, const double* sift,
+                             const double* G1, const double* G2, size_t n, const double extent[4],
+                             uint64_t local_iterations, uint64_t seed, uint64_t slot0, uint32_t nslots, int threads,
+                             uint8_t* inc_out, double* models_out);
 /* host-only: the check gcr_problem_set_probabilities makes of its weights for
  * a minimal sample of m (GCR_OK, or GCR_EINVAL with a message) */
 int gcr_host_check_probabilities(const double* probabilities, size_t n, uint32_t m);
