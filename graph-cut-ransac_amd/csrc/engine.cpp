@@ -61,6 +61,7 @@
 #include "sifth.h"
 #include "graphcut.h"
 #include "host_pool.h"
+#include "match.h"
 
 using namespace gcr;
 
@@ -6320,6 +6321,46 @@ int gcr_warp_perspective(gcr_ctx* ctx, const void* src, int src_h, int src_w, in
         HIPC(e);
         return GCR_OK;
     });
+}
+
+int gcr_match_descriptors(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim,
+                          uint32_t* idx_out, uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out,
+                          double* ms_kernel_out) {
+    if (const char* bad = match_check_args(d1, n1, d2, n2, dim, idx_out, dist_out, idx2_out, dist2_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    if (!ctx) return set_err(GCR_EINVAL, "null context");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(match_device(ctx->stream, ctx->n_cu, d1, n1, d2, n2, dim, idx_out, dist_out, idx2_out, dist2_out,
+                          ms_kernel_out));
+        return GCR_OK;
+    });
+}
+
+int gcr_host_match_descriptors(const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim, int threads,
+                               uint32_t* idx_out, uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out) {
+    if (const char* bad = match_check_args(d1, n1, d2, n2, dim, idx_out, dist_out, idx2_out, dist2_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    return guard([&]() -> int {
+        const size_t nt = std::min<size_t>(n1, (size_t)std::max(1, std::min(threads, 64)));
+        const size_t step = (n1 + nt - 1) / nt;
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < nt; ++t)
+            pool.emplace_back([=] {
+                host_match_rows(d1, d2, n2, dim, std::min(n1, t * step), std::min(n1, (t + 1) * step), idx_out,
+                                dist_out, idx2_out, dist2_out);
+            });
+        host_match_rows(d1, d2, n2, dim, 0, std::min(n1, step), idx_out, dist_out, idx2_out, dist2_out);
+        for (auto& th : pool) th.join();
+        return GCR_OK;
+    });
+}
+
+void gcr_match_tiling(uint32_t out[3]) {
+    if (!out) return;
+    out[0] = kMatchRowsPerWg;
+    out[1] = kMatchStepCols;
+    out[2] = kMatchSplitMinCols;
 }
 
 int gcr_host_grid_edges(const double* points, size_t n, int dims, const double* cell_size, uint64_t cell_number,

@@ -259,6 +259,11 @@ def _load():
     L.gcr_host_check_sift.argtypes = [vp, C.c_size_t]
     L.gcr_host_solve_s2.argtypes = [vp, vp, C.c_size_t, vp, vp, u32p]
     L.gcr_host_generate_s.argtypes = [vp, vp, C.c_size_t, vp, C.c_uint64, C.c_uint64, C.c_uint32, C.c_int, vp, vp]
+    # descriptor matching (csrc/match.h): uint8 descriptors in, idx / dist / idx2 / dist2 (uint32) out
+    L.gcr_match_descriptors.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp, dp]
+    L.gcr_host_match_descriptors.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_int, vp, vp, vp, vp]
+    L.gcr_match_tiling.argtypes = [u32p]
+    L.gcr_match_tiling.restype = None
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

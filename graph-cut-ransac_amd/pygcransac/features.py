@@ -6,13 +6,20 @@ with .pt, .size and .angle works, and so does an (N, 4) array of
 (x, y, size, angle_degrees) rows (angle -1 = none, OpenCV's convention).
 `perspective_warp` rectifies an image with the estimated homography on the
 GPU (a HIP resampling kernel behind gcr_warp_perspective), cv2-free.
+
+`match_descriptors` is the step before the estimators: exact 2-nearest-
+neighbour matching of uint8 (SIFT-style) descriptors on the GPU's int8 matrix
+cores (gcr_match_descriptors, csrc/match.h), with the ratio test and the
+mutual check.  `quantize_descriptors` brings float descriptors to uint8 and
+`correspondences_from_matches` builds the estimators' rows from the matches.
 """
 from __future__ import annotations
 
 import numpy as np
 
 __all__ = ["scale_features_from_sift", "orientation_features_from_sift", "keypoints_to_array", "perspective_warp",
-           "warp_geometry", "BORDER_CONSTANT", "BORDER_REPLICATE"]
+           "warp_geometry", "BORDER_CONSTANT", "BORDER_REPLICATE", "match_descriptors", "quantize_descriptors",
+           "correspondences_from_matches"]
 
 # OpenCV's border codes (cv2.BORDER_CONSTANT = 0, cv2.BORDER_REPLICATE = 1)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
@@ -114,3 +121,124 @@ def perspective_warp(img, H, border_mode=BORDER_CONSTANT, border_value=(255, 255
     N.check(N.lib.gcr_warp_perspective(N.context(device), src.ctypes.data, h, w, ch, dtype, M.ctypes.data_as(dp),
                                        int(border_mode), bv.ctypes.data_as(dp), out.ctypes.data, oh, ow))
     return out, Ht, mins
+
+
+def quantize_descriptors(desc, scale: float = 512.0) -> np.ndarray:
+    """uint8 descriptors from float ones: ``clip(rint(scale * x), 0, 255)``.
+    The default scale is the usual one for unit-norm 128-d descriptors (SIFT,
+    RootSIFT), whose components rarely pass 0.5."""
+    a = np.asarray(desc, dtype=np.float64)
+    if a.ndim != 2:
+        raise ValueError("descriptors must have shape (N, dim)")
+    if not np.isfinite(a).all():
+        raise ValueError("descriptors must be finite")
+    return np.clip(np.rint(float(scale) * a), 0.0, 255.0).astype(np.uint8)
+
+
+def _as_descriptors(desc, name):
+    a = np.asarray(desc)
+    if a.dtype != np.uint8:
+        raise ValueError(f"{name} must be a uint8 array, got {a.dtype}; quantize_descriptors() converts float "
+                         "descriptors")
+    if a.ndim != 2:
+        raise ValueError(f"{name} must have shape (N, dim), got {a.shape}")
+    return np.ascontiguousarray(a)
+
+
+def _nearest_two(d1, d2, backend, device):
+    """idx, dist, idx2, dist2 (uint32, one per row of d1) by the engine."""
+    from . import _native as N
+
+    n1, dim = d1.shape
+    out = [np.empty(n1, dtype=np.uint32) for _ in range(4)]
+    ptrs = [o.ctypes.data for o in out]
+    if backend == "host":
+        import os
+
+        threads = max(1, min(16, os.cpu_count() or 1))
+        N.check(N.lib.gcr_host_match_descriptors(d1.ctypes.data, n1, d2.ctypes.data, d2.shape[0], dim, threads, *ptrs))
+    else:
+        N.check(N.lib.gcr_match_descriptors(N.context(device), d1.ctypes.data, n1, d2.ctypes.data, d2.shape[0], dim,
+                                            *ptrs, None))
+    return out
+
+
+def match_descriptors(desc1, desc2, ratio=0.8, mutual=True, *, backend="gpu", device=None):
+    """Match two sets of uint8 descriptors: exact nearest and second-nearest
+    neighbour of every row of ``desc1`` among the rows of ``desc2`` under the
+    squared Euclidean distance (an integer; on equal distances the lower index
+    is nearer), Lowe's ratio test and the mutual-nearest check.
+
+    ``desc1`` is (n1, dim) and ``desc2`` (n2, dim), both uint8 (anything else
+    is a ValueError: ``quantize_descriptors`` converts float descriptors);
+    ``dim`` is a multiple of 32 in 32..512.  A pair (i, j) passes the ratio
+    test iff ``float(dist) < (ratio * ratio) * float(dist2)`` in float64, where
+    dist2 is the distance to i's second neighbour; with no second neighbour
+    (n2 == 1) it fails.  ``ratio=None`` skips the test.  ``mutual=True`` keeps
+    (i, j) iff j is i's nearest and i is j's nearest (a second matching with
+    the arguments swapped, the same tie rule).  ``backend="gpu"`` runs the HIP
+    kernels (csrc/match.hip: int8 matrix cores, exact), ``backend="host"`` the
+    plain-loop definition on up to 16 threads, without a GPU; both give the
+    same bytes.
+
+    Returns ``(matches, ratios)``: ``matches`` (M, 2) int64 rows (i, j) sorted
+    by i, ``ratios`` (M,) float64 with sqrt(dist / dist2) (1.0 for 0 / 0 and
+    where there is no second neighbour).  ``-ratios`` is a valid
+    ``probabilities`` for the estimators' ``sampler=1`` (PROSAC): a quality
+    score per correspondence, higher is better."""
+    d1 = _as_descriptors(desc1, "desc1")
+    d2 = _as_descriptors(desc2, "desc2")
+    if d1.shape[1] != d2.shape[1]:
+        raise ValueError(f"desc1 and desc2 differ in dimension: {d1.shape[1]} and {d2.shape[1]}")
+    if d1.shape[1] % 32 or not 32 <= d1.shape[1] <= 512:
+        raise ValueError(f"the descriptor dimension must be a multiple of 32 in 32..512, got {d1.shape[1]}")
+    if d1.shape[0] == 0 or d2.shape[0] == 0:
+        raise ValueError("desc1 and desc2 need at least one row each")
+    if backend not in ("gpu", "host"):
+        raise ValueError(f"backend must be 'gpu' or 'host', got {backend!r}")
+    if ratio is not None and not (np.isfinite(ratio) and ratio > 0):
+        raise ValueError("ratio must be None or a finite number > 0")
+    idx, dist, idx2, dist2 = _nearest_two(d1, d2, backend, device)
+    none = idx2 == 0xFFFFFFFF
+    fd, fd2 = dist.astype(np.float64), dist2.astype(np.float64)
+    ratios = np.ones(len(idx), dtype=np.float64)
+    ok = ~none & (fd2 > 0)
+    ratios[ok] = np.sqrt(fd[ok] / fd2[ok])
+    keep = np.ones(len(idx), dtype=bool)
+    if ratio is not None:
+        keep &= ~none & (fd < (float(ratio) * float(ratio)) * fd2)
+    if mutual:
+        back = _nearest_two(d2, d1, backend, device)[0]
+        keep &= back[idx] == np.arange(len(idx), dtype=np.uint32)
+    rows = np.nonzero(keep)[0]
+    matches = np.stack([rows.astype(np.int64), idx[rows].astype(np.int64)], axis=1)
+    return matches, ratios[rows]
+
+
+def correspondences_from_matches(kp1, kp2, matches, sift=False) -> np.ndarray:
+    """The estimators' rows from matched keypoints.  ``kp1`` / ``kp2`` are read
+    as by ``keypoints_to_array``, ``matches`` is (M, 2) rows (i, j) into them.
+
+    Returns (M, 4) float64 rows x1, y1, x2, y2 (findHomography,
+    findFundamentalMatrix, ...); with ``sift=True`` the (M, 8) rows
+    findHomographySIFT takes: x1, y1, x2, y2, q1, q2, alpha1, alpha2 with the
+    keypoint sizes as the lengths q and the orientations in RADIANS.  A
+    matched keypoint without an angle (-1, OpenCV's convention) is then a
+    ValueError."""
+    a, b = keypoints_to_array(kp1), keypoints_to_array(kp2)
+    m = np.asarray(matches)
+    if m.ndim != 2 or m.shape[1] != 2:
+        raise ValueError("matches must have shape (M, 2): rows (i, j)")
+    if m.size and not np.issubdtype(m.dtype, np.integer):
+        raise ValueError("matches must be an integer array")
+    m = m.astype(np.int64)
+    if m.size and (m.min() < 0 or m[:, 0].max() >= len(a) or m[:, 1].max() >= len(b)):
+        raise ValueError("matches index past the keypoints")
+    r1, r2 = a[m[:, 0]], b[m[:, 1]]
+    if not sift:
+        return np.ascontiguousarray(np.column_stack([r1[:, 0], r1[:, 1], r2[:, 0], r2[:, 1]]))
+    bad = int(((r1[:, 3] == -1) | (r2[:, 3] == -1)).sum())
+    if bad:
+        raise ValueError(f"{bad} matched keypoints have no orientation (angle -1)")
+    return np.ascontiguousarray(np.column_stack([r1[:, 0], r1[:, 1], r2[:, 0], r2[:, 1], r1[:, 2], r2[:, 2],
+                                                 np.deg2rad(r1[:, 3]), np.deg2rad(r2[:, 3])]))

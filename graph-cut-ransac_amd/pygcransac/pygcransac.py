@@ -625,7 +625,8 @@ def findHomography(correspondences, h1, w1, h2, w2, probabilities=None, threshol
     the sum.  ``sampler=1`` is PROSAC (upstream's sampler 1; csrc/prosac.h is
     the definition): ``probabilities`` then holds one quality score per
     correspondence, higher is better, every value finite (a SIFT ratio-test
-    value negated, a descriptor similarity; rows already in quality order:
+    value negated -- ``-ratios`` of ``features.match_descriptors`` is one --,
+    a descriptor similarity; rows already in quality order:
     ``-np.arange(n)``; scores that are all equal rank nothing and are a
     ValueError).  The rows are sorted by score descending (stable: ties
     keep their order), early iterations sample among the best-ranked rows, the

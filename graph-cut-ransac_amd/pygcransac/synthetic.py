@@ -316,3 +316,47 @@ def problem_hs(n: int = 5_000, outlier_ratio: float = 0.5, seed: int = DEFAULT_S
     a2 = np.where(truth, a2_in, a2)
     q2 = np.where(truth, q2_in, q2)
     return np.ascontiguousarray(np.column_stack([corr, q1, q2, a1, a2])), truth, Hgt, thr
+
+
+def problem_match(n: int = 1_000, shared: int = 400, seed: int = DEFAULT_SEED, desc_noise: float = 40.0,
+                  dim: int = 128):
+    """Two images' keypoints and uint8 descriptors, for match_descriptors and
+    the estimators behind it.  Each image has n keypoints (x, y, size,
+    angle_deg); `shared` of them are the same scene points: related by
+    problem_hs's geometry (H_GT, its pixel, size and orientation noise), their
+    descriptors one uniform random byte vector per scene point plus Gaussian
+    noise of `desc_noise` per image, rounded and clipped to 0..255.  The other
+    n - shared keypoints of each image are independent (uniform positions
+    and descriptors).  Image 2 is permuted.
+
+    Returns (kp1 (n, 4), desc1 (n, dim) uint8, kp2, desc2, pairs (shared, 2)
+    int64 rows (i, j) sorted by i, H_gt)."""
+    if not 0 <= shared <= n:
+        raise ValueError("need 0 <= shared <= n")
+    c8, _, Hgt, _ = problem_hs(shared, 0.0, seed) if shared else (np.zeros((0, 8)), None, H_GT.copy(), None)
+    rng = np.random.default_rng([seed, 0x6d617463])
+    rest = n - shared
+
+    def independent(k):
+        return np.column_stack([rng.uniform(0, IMG_W, k), rng.uniform(0, IMG_H, k),
+                                np.exp(rng.uniform(math.log(2.0), math.log(30.0), k)),
+                                np.degrees(rng.uniform(-math.pi, math.pi, k))])
+
+    kp1 = np.concatenate([np.column_stack([c8[:, 0], c8[:, 1], c8[:, 4], np.degrees(c8[:, 6])]), independent(rest)])
+    kp2 = np.concatenate([np.column_stack([c8[:, 2], c8[:, 3], c8[:, 5], np.degrees(c8[:, 7])]), independent(rest)])
+    base = rng.integers(0, 256, (shared, dim)).astype(np.float64)
+
+    def noisy():
+        return np.clip(np.rint(base + rng.normal(0.0, desc_noise, base.shape)), 0, 255).astype(np.uint8)
+
+    desc1 = np.concatenate([noisy(), rng.integers(0, 256, (rest, dim), dtype=np.uint8)])
+    desc2 = np.concatenate([noisy(), rng.integers(0, 256, (rest, dim), dtype=np.uint8)])
+    # image 1 is shuffled too, so that the shared keypoints are not its first rows
+    p1, p2 = rng.permutation(n), rng.permutation(n)
+    inv1, inv2 = np.empty(n, np.int64), np.empty(n, np.int64)
+    inv1[p1] = np.arange(n)
+    inv2[p2] = np.arange(n)
+    pairs = np.stack([inv1[:shared], inv2[:shared]], axis=1)
+    pairs = pairs[np.argsort(pairs[:, 0], kind="stable")]
+    return (np.ascontiguousarray(kp1[p1]), np.ascontiguousarray(desc1[p1]), np.ascontiguousarray(kp2[p2]),
+            np.ascontiguousarray(desc2[p2]), pairs, Hgt)

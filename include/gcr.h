@@ -735,6 +735,29 @@ int gcr_debug_math(gcr_ctx* ctx, int op, const double* a, const double* b, size_
 int gcr_warp_perspective(gcr_ctx* ctx, const void* src, int src_h, int src_w, int channels, int dtype,
                          const double M[9], int border_mode, const double border_value[4], void* dst, int dst_h,
                          int dst_w);
+/* Exact 2-nearest-neighbour matching of uint8 descriptors (csrc/match.h is
+ * the definition, csrc/match.hip the int8 matrix-core kernels).  d1 is n1 x
+ * dim, d2 is n2 x dim, row-major host buffers; dim is a multiple of 32 in
+ * 32..512; 1 <= n1, n2 <= 2^24.  d(i, j) = sum_k (d1[i,k] - d2[j,k])^2.  For
+ * every row i of d1 the neighbours are ordered by (d(i, j), j) -- on a tie the
+ * lower index is nearer -- and idx_out / dist_out take the first, idx2_out /
+ * dist2_out the second element of that order (0xFFFFFFFF both for n2 == 1);
+ * n1 values each.  The device result equals gcr_host_match_descriptors' bit
+ * for bit.  A NULL buffer, a bad n1, n2 or dim is GCR_EINVAL with a message
+ * naming the argument, before any GPU work (so also with a NULL context).
+ * GCR_MATCH_SPLIT=k in the environment pins the number of column splits
+ * (tests).  ms_kernel_out may be NULL: HIP-event time of the kernels. */
+int gcr_match_descriptors(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim,
+                          uint32_t* idx_out, uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out,
+                          double* ms_kernel_out);
+/* host-only: the same by plain loops; `threads` (clamped to 1..64) splits the
+ * rows of d1 only and does not change the result */
+int gcr_host_match_descriptors(const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim, int threads,
+                               uint32_t* idx_out, uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out);
+/* the matcher kernels' tiling, for tests at its edges: out[0] = rows of d1 per
+ * workgroup, out[1] = rows of d2 (columns) per step, out[2] = the least
+ * columns per split the planner chooses */
+void gcr_match_tiling(uint32_t out[3]);
 /* measurement (bench.py): achievable HBM bandwidth of the device, GB/s of
  * read + write traffic of a streaming device-to-device copy of `bytes` bytes,
  * best of `iters` timed copies of each of two variants, plain and nontemporal
