@@ -62,6 +62,7 @@
 #include "graphcut.h"
 #include "host_pool.h"
 #include "match.h"
+#include "match_geo.h"
 
 using namespace gcr;
 
@@ -6351,6 +6352,50 @@ int gcr_host_match_descriptors(const uint8_t* d1, size_t n1, const uint8_t* d2, 
                                 dist_out, idx2_out, dist2_out);
             });
         host_match_rows(d1, d2, n2, dim, 0, std::min(n1, step), idx_out, dist_out, idx2_out, dist2_out);
+        for (auto& th : pool) th.join();
+        return GCR_OK;
+    });
+}
+
+static_assert(kMatchGeoHomography == GCR_SOLVER_HOMOGRAPHY4 && kMatchGeoFundamental == GCR_SOLVER_FUNDAMENTAL7 &&
+                  kMatchGeoHomography == kKindHomography && kMatchGeoFundamental == kKindFundamental,
+              "match_geo.h's kinds are the two residual kinds of solver.h");
+
+int gcr_match_descriptors_guided(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const double* p1, const uint8_t* d2,
+                                 size_t n2, const double* p2, uint32_t dim, int kind, const double* model,
+                                 double sq_threshold, int reverse, uint32_t* idx_out, uint32_t* dist_out,
+                                 uint32_t* idx2_out, uint32_t* dist2_out, double* ms_kernel_out) {
+    if (const char* bad = match_geo_check_args(d1, n1, p1, d2, n2, p2, dim, kind, model, sq_threshold, reverse, idx_out,
+                                               dist_out, idx2_out, dist2_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    if (!ctx) return set_err(GCR_EINVAL, "null context");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(match_geo_device(ctx->stream, ctx->n_cu, d1, n1, p1, d2, n2, p2, dim, kind, model, sq_threshold, reverse,
+                              idx_out, dist_out, idx2_out, dist2_out, ms_kernel_out));
+        return GCR_OK;
+    });
+}
+
+int gcr_host_match_descriptors_guided(const uint8_t* d1, size_t n1, const double* p1, const uint8_t* d2, size_t n2,
+                                      const double* p2, uint32_t dim, int kind, const double* model,
+                                      double sq_threshold, int reverse, int threads, uint32_t* idx_out,
+                                      uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out) {
+    if (const char* bad = match_geo_check_args(d1, n1, p1, d2, n2, p2, dim, kind, model, sq_threshold, reverse, idx_out,
+                                               dist_out, idx2_out, dist2_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    return guard([&]() -> int {
+        const size_t nr = reverse ? n2 : n1;
+        const size_t nt = std::min<size_t>(nr, (size_t)std::max(1, std::min(threads, 64)));
+        const size_t step = (nr + nt - 1) / nt;
+        auto rows = [=](size_t r0, size_t r1) {
+            host_match_rows_guided(d1, n1, p1, d2, n2, p2, dim, kind, model, sq_threshold, reverse, r0, r1, idx_out,
+                                   dist_out, idx2_out, dist2_out);
+        };
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < nt; ++t)
+            pool.emplace_back([=] { rows(std::min(nr, t * step), std::min(nr, (t + 1) * step)); });
+        rows(0, std::min(nr, step));
         for (auto& th : pool) th.join();
         return GCR_OK;
     });

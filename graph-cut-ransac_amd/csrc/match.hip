@@ -32,12 +32,31 @@
 //                  then writes the result itself.
 // Device memory beyond the descriptors: norms, results and the partials,
 // O(n1 * splits + n2).  The n1 x n2 matrix never exists.
+//
+// Guided matching (match_geo.h is the definition; gcr_match_descriptors_guided
+// the entry) adds two kernels and reuses k_match_norms and k_match_merge:
+//   k_match_geo_terms  the factorised residual's per-point terms, four doubles
+//                      per keypoint of either image, one thread per keypoint.
+//   k_match_geo<NK>    k_match's tiling.  The kernel's ROWS are the result
+//                      rows (image 1 forward, image 2 in reverse), its columns
+//                      the other image.  A lane keeps its row's terms in
+//                      registers; a step first stages its 64 columns' terms in
+//                      the LDS and every lane evaluates the admissibility of
+//                      its 2 x 16 pairs into two 16-bit masks.  Padded columns
+//                      and padded rows are cleared from the masks by INDEX
+//                      (their clamped positions are real keypoints').  A step
+//                      in which no wave of the workgroup has an admissible pair
+//                      stages no descriptors at all; a tile in which the wave
+//                      has none runs no MFMA.  An inadmissible pair's e is
+//                      INT_MAX before the minimum / __any / update sequence,
+//                      which is k_match's.
 #include <hip/hip_runtime.h>
 
 #include <climits>
 #include <cstdlib>
 
 #include "match.h"
+#include "match_geo.h"
 
 namespace gcr {
 namespace {
@@ -225,6 +244,237 @@ constexpr LaunchFn kLaunch[16] = {
     launch_k_match<13>, launch_k_match<14>, launch_k_match<15>, launch_k_match<16>,
 };
 
+// ------------------------------------------------------------ guided matching --
+struct MatchGeoArgs {
+    MatchArgs m;                // d1 / norm1 / n1: the image of the result rows; d2 / norm2 / n2: the columns'
+    const double* row_terms;    // [m.n1][kMatchGeoTerms]
+    const double* col_terms;    // [m.n2][kMatchGeoTerms]
+    double T;
+    int kind, reverse;          // reverse: the rows are image 2
+};
+
+struct MatchGeoModel {
+    double h[9];
+};
+
+// t1: the terms of image 1's keypoints, t2: of image 2's (whatever the direction)
+__global__ __launch_bounds__(kMatchThreads) void k_match_geo_terms(const double* p1, uint32_t n1, const double* p2,
+                                                                   uint32_t n2, MatchGeoModel mdl, int kind,
+                                                                   double* t1, double* t2) {
+    const uint32_t t = blockIdx.x * kMatchThreads + threadIdx.x;
+    if (t >= n1 + n2) return;
+    const bool first = t < n1;
+    const uint32_t k = first ? t : t - n1;
+    const double* p = (first ? p1 : p2) + 2 * (size_t)k;
+    const double x = p[0], y = p[1];
+    double v[kMatchGeoTerms];
+    if (kind == kMatchGeoFundamental) {
+        if (first) match_geo_terms1<kMatchGeoFundamental>(x, y, mdl.h, v);
+        else match_geo_terms2<kMatchGeoFundamental>(x, y, mdl.h, v);
+    } else {
+        if (first) match_geo_terms1<kMatchGeoHomography>(x, y, mdl.h, v);
+        else match_geo_terms2<kMatchGeoHomography>(x, y, mdl.h, v);
+    }
+    double* o = (first ? t1 : t2) + kMatchGeoTerms * (size_t)k;
+#pragma unroll
+    for (int q = 0; q < kMatchGeoTerms; ++q) o[q] = v[q];
+}
+
+// Bit reg of the result: the pair of the lane's row (terms rt) and the column
+// (reg & 3) + 8 (reg >> 2) past ct's is admissible.  REV: the row is image 2's.
+template <int KIND, bool REV>
+__device__ __forceinline__ uint32_t geo_tile_mask(const double (&rt)[kMatchGeoTerms], const double* ct, double T) {
+    uint32_t m = 0;
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) {
+        const double* c = ct + ((reg & 3) + 8 * (reg >> 2)) * kMatchGeoTerms;
+        double cv[kMatchGeoTerms] = {c[0], c[1], 0.0, 0.0};
+        if constexpr (KIND == kMatchGeoFundamental) {
+            cv[2] = c[2];
+            cv[3] = c[3];
+        }
+        const bool adm = REV ? match_geo_adm<KIND>(cv, rt, T) : match_geo_adm<KIND>(rt, cv, T);
+        m |= adm ? 1u << reg : 0u;
+    }
+    return m;
+}
+
+template <int NK>
+__global__ __launch_bounds__(kMatchThreads) void k_match_geo(MatchGeoArgs g) {
+    constexpr uint32_t DIM = NK * 32;
+    constexpr uint32_t STRIDE = DIM + 16;                 // as k_match
+    constexpr uint32_t CHUNKS = DIM / 16;
+    static_assert(kMatchStepCols * kMatchGeoTerms == kMatchThreads, "one term per thread and step");
+    __shared__ __attribute__((aligned(16))) uint8_t s_d2[kMatchStepCols * STRIDE];
+    __shared__ __attribute__((aligned(16))) int s_nb[kMatchStepCols];
+    // the steps alternate between two copies of the terms and of the flag: a
+    // step's writes never meet the previous step's reads
+    __shared__ __attribute__((aligned(16))) double s_ct[2][kMatchStepCols * kMatchGeoTerms];
+    __shared__ int s_need[2];
+
+    const MatchArgs& a = g.m;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t lane = tid & 63u, wave = tid >> 6;
+    const uint32_t r = lane & 31u, h = lane >> 5;
+    const uint32_t rb = blockIdx.x / a.splits, sp = blockIdx.x % a.splits;
+    const uint32_t i = rb * kMatchRowsPerWg + wave * 32u + r;
+    const bool row_ok = i < a.n1;
+    const uint32_t ic = row_ok ? i : a.n1 - 1;            // rows past the end read the last row, never written
+
+    v4i breg[NK];
+    {
+        const uint4* p = reinterpret_cast<const uint4*>(a.d1 + (size_t)ic * DIM + h * 16u);
+#pragma unroll
+        for (int ks = 0; ks < NK; ++ks) {
+            const uint4 v = p[2 * ks];
+            breg[ks] = v4i{(int)(v.x ^ kSignFlip), (int)(v.y ^ kSignFlip), (int)(v.z ^ kSignFlip),
+                           (int)(v.w ^ kSignFlip)};
+        }
+    }
+    double rt[kMatchGeoTerms];
+#pragma unroll
+    for (int q = 0; q < kMatchGeoTerms; ++q) rt[q] = g.row_terms[(size_t)ic * kMatchGeoTerms + q];
+    const double T = g.T;
+    const int mode = (g.kind == kMatchGeoFundamental ? 2 : 0) + (g.reverse ? 1 : 0);    // workgroup-uniform
+
+    const uint32_t jbeg = sp * a.cols;
+    const uint32_t jend = jbeg + a.cols < a.n2 ? jbeg + a.cols : a.n2;
+
+    int e1 = INT_MAX, e2 = INT_MAX;
+    uint32_t j1 = kMatchNone, j2 = kMatchNone;
+
+    uint32_t par = 0;
+    for (uint32_t j0 = jbeg; j0 < jend; j0 += kMatchStepCols, par ^= 1u) {
+        double* ct = s_ct[par];
+        {
+            const uint32_t col = tid / kMatchGeoTerms;
+            const uint32_t j = j0 + col < a.n2 ? j0 + col : a.n2 - 1;
+            ct[tid] = g.col_terms[(size_t)j * kMatchGeoTerms + tid % kMatchGeoTerms];
+        }
+        if (tid == 0) s_need[par] = 0;
+        __syncthreads();
+        // admissibility of the lane's 16 columns of either tile
+        uint32_t adm[kMatchStepCols / 32u];
+#pragma unroll
+        for (uint32_t q = 0; q < kMatchStepCols / 32u; ++q) {
+            const uint32_t jt = j0 + q * 32u;             // wave-uniform
+            adm[q] = 0;
+            if (jt >= jend) continue;
+            const double* c0 = ct + (q * 32u + 4u * h) * kMatchGeoTerms;
+            uint32_t m;
+            switch (mode) {
+                case 0: m = geo_tile_mask<kMatchGeoHomography, false>(rt, c0, T); break;
+                case 1: m = geo_tile_mask<kMatchGeoHomography, true>(rt, c0, T); break;
+                case 2: m = geo_tile_mask<kMatchGeoFundamental, false>(rt, c0, T); break;
+                default: m = geo_tile_mask<kMatchGeoFundamental, true>(rt, c0, T); break;
+            }
+            // padded columns and padded rows leave by index: their terms are a real keypoint's
+            if (jt + 32u > jend) {
+                const uint32_t jl = jt + 4u * h;
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg)
+                    if (jl + (reg & 3) + 8 * (reg >> 2) >= jend) m &= ~(1u << reg);
+            }
+            adm[q] = row_ok ? m : 0u;
+        }
+        bool wany[kMatchStepCols / 32u];
+        bool any = false;
+#pragma unroll
+        for (uint32_t q = 0; q < kMatchStepCols / 32u; ++q) {
+            wany[q] = __any(adm[q] != 0u);                // wave-uniform
+            any |= wany[q];
+        }
+        if (any && lane == 0) s_need[par] = 1;
+        __syncthreads();
+        if (!s_need[par]) continue;                       // no admissible pair in the whole step: nothing staged
+
+        for (uint32_t c = tid; c < kMatchStepCols * CHUNKS; c += kMatchThreads) {
+            const uint32_t col = c / CHUNKS, off = (c % CHUNKS) * 16u;
+            const uint32_t j = j0 + col < a.n2 ? j0 + col : a.n2 - 1;
+            uint4 v = *reinterpret_cast<const uint4*>(a.d2 + (size_t)j * DIM + off);
+            v.x ^= kSignFlip;
+            v.y ^= kSignFlip;
+            v.z ^= kSignFlip;
+            v.w ^= kSignFlip;
+            *reinterpret_cast<uint4*>(&s_d2[col * STRIDE + off]) = v;
+        }
+        if (tid < kMatchStepCols) {
+            const uint32_t j = j0 + tid < a.n2 ? j0 + tid : a.n2 - 1;
+            s_nb[tid] = (int)a.norm2[j];
+        }
+        __syncthreads();
+#pragma unroll
+        for (uint32_t q = 0; q < kMatchStepCols / 32u; ++q) {
+            if (!wany[q]) continue;                       // the wave has no admissible pair in the tile: no MFMA
+            const uint32_t jt = j0 + q * 32u;
+            v16i acc = {};
+            const uint8_t* arow = &s_d2[(q * 32u + r) * STRIDE + h * 16u];
+#pragma unroll
+            for (int ks = 0; ks < NK; ++ks) {
+                const v4i av = *reinterpret_cast<const v4i*>(arow + ks * 32);
+                acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(av, breg[ks], acc, 0, 0, 0);
+            }
+            int e[16];
+#pragma unroll
+            for (int gq = 0; gq < 4; ++gq) {
+                const v4i nb = *reinterpret_cast<const v4i*>(&s_nb[q * 32u + 8u * gq + 4u * h]);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    e[4 * gq + k] = (adm[q] >> (4 * gq + k)) & 1u ? nb[k] - 2 * acc[4 * gq + k] : INT_MAX;
+            }
+            const uint32_t jl = jt + 4u * h;              // the lane's first column of the tile
+            int m = e[0];
+#pragma unroll
+            for (int reg = 1; reg < 16; ++reg) m = e[reg] < m ? e[reg] : m;
+            if (__any(m < e2)) {
+#pragma unroll
+                for (int reg = 0; reg < 16; ++reg) {
+                    const int ev = e[reg];
+                    const uint32_t jj = jl + (reg & 3) + 8 * (reg >> 2);
+                    if (ev < e1) {
+                        e2 = e1;
+                        j2 = j1;
+                        e1 = ev;
+                        j1 = jj;
+                    } else if (ev < e2) {
+                        e2 = ev;
+                        j2 = jj;
+                    }
+                }
+            }
+        }
+    }
+
+    // the two lane halves hold disjoint columns of the same row
+    const int na = (int)a.norm1[ic];
+    const uint32_t da = e1 == INT_MAX ? kMatchNone : (uint32_t)(e1 + na);
+    const uint32_t db = e2 == INT_MAX ? kMatchNone : (uint32_t)(e2 + na);
+    uint64_t k1 = match_key(da, j1), k2 = match_key(db, j2);
+    const uint64_t o1 = match_key((uint32_t)__shfl_xor((int)da, 32), (uint32_t)__shfl_xor((int)j1, 32));
+    const uint64_t o2 = match_key((uint32_t)__shfl_xor((int)db, 32), (uint32_t)__shfl_xor((int)j2, 32));
+    match_merge(k1, k2, o1, o2);
+    if (h == 0 && row_ok) {
+        const size_t o = (size_t)sp * a.n1 + i;
+        a.p_idx[o] = (uint32_t)k1;
+        a.p_dist[o] = (uint32_t)(k1 >> 32);
+        a.p_idx2[o] = (uint32_t)k2;
+        a.p_dist2[o] = (uint32_t)(k2 >> 32);
+    }
+}
+
+template <int NK>
+void launch_k_match_geo(const MatchGeoArgs& g, uint32_t blocks, hipStream_t stream) {
+    hipLaunchKernelGGL(k_match_geo<NK>, dim3(blocks), dim3(kMatchThreads), 0, stream, g);
+}
+
+using LaunchGeoFn = void (*)(const MatchGeoArgs&, uint32_t, hipStream_t);
+constexpr LaunchGeoFn kLaunchGeo[16] = {
+    launch_k_match_geo<1>,  launch_k_match_geo<2>,  launch_k_match_geo<3>,  launch_k_match_geo<4>,
+    launch_k_match_geo<5>,  launch_k_match_geo<6>,  launch_k_match_geo<7>,  launch_k_match_geo<8>,
+    launch_k_match_geo<9>,  launch_k_match_geo<10>, launch_k_match_geo<11>, launch_k_match_geo<12>,
+    launch_k_match_geo<13>, launch_k_match_geo<14>, launch_k_match_geo<15>, launch_k_match_geo<16>,
+};
+
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
 }  // namespace
@@ -299,6 +549,116 @@ hipError_t match_device(hipStream_t stream, int n_cu, const uint8_t* d1, size_t 
     if (e == hipSuccess) e = hipMemcpyAsync(dist, a.dist, n1 * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(idx2, a.idx2, n1 * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dist2, a.dist2, n1 * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess && ms_kernel) {
+        float ms = 0.f;
+        e = hipEventElapsedTime(&ms, ev0, ev1);
+        *ms_kernel = (double)ms;
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(stream);    // nothing in flight reads `base` past the free
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipFree(base);
+    return e;
+}
+
+hipError_t match_geo_device(hipStream_t stream, int n_cu, const uint8_t* d1, size_t n1, const double* p1,
+                            const uint8_t* d2, size_t n2, const double* p2, uint32_t dim, int kind, const double* model,
+                            double sq_threshold, int reverse, uint32_t* idx, uint32_t* dist, uint32_t* idx2,
+                            uint32_t* dist2, double* ms_kernel) {
+    int pin = 0;                                          // GCR_MATCH_SPLIT, as match_device
+    if (const char* e = getenv("GCR_MATCH_SPLIT")) {
+        const int v = atoi(e);
+        if (v >= 1) pin = v < 1024 ? v : 1024;
+    }
+    // the kernels' rows are the result rows, their columns the other image
+    const size_t nr = reverse ? n2 : n1, nc = reverse ? n1 : n2;
+    const uint8_t* dr = reverse ? d2 : d1;
+    const uint8_t* dc = reverse ? d1 : d2;
+    uint32_t cols = 0;
+    const uint32_t splits = match_plan(nr, nc, n_cu, pin, &cols);
+    const size_t row_blocks = (nr + kMatchRowsPerWg - 1) / kMatchRowsPerWg;
+
+    const size_t b_dr = up256(nr * dim), b_dc = up256(nc * dim);
+    const size_t b_nr = up256(nr * 4), b_nc = up256(nc * 4);
+    const size_t b_p1 = up256(n1 * 2 * sizeof(double)), b_p2 = up256(n2 * 2 * sizeof(double));
+    const size_t b_t1 = up256(n1 * kMatchGeoTerms * sizeof(double)), b_t2 = up256(n2 * kMatchGeoTerms * sizeof(double));
+    const size_t b_out = up256(nr * 4), b_part = splits > 1 ? up256((size_t)splits * nr * 4) : 0;
+    char* base = nullptr;
+    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base),
+                             b_p1 + b_p2 + b_t1 + b_t2 + b_dr + b_dc + b_nr + b_nc + 4 * b_out + 4 * b_part);
+    if (e != hipSuccess) return e;
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    MatchGeoArgs g{};
+    MatchArgs& a = g.m;
+    char* p = base;                                       // the doubles first: 256-byte aligned either way
+    double* dp1 = reinterpret_cast<double*>(p);
+    p += b_p1;
+    double* dp2 = reinterpret_cast<double*>(p);
+    p += b_p2;
+    double* t1 = reinterpret_cast<double*>(p);
+    p += b_t1;
+    double* t2 = reinterpret_cast<double*>(p);
+    p += b_t2;
+    a.d1 = reinterpret_cast<uint8_t*>(p), p += b_dr;
+    a.d2 = reinterpret_cast<uint8_t*>(p), p += b_dc;
+    uint32_t* norm1 = reinterpret_cast<uint32_t*>(p);
+    p += b_nr;
+    uint32_t* norm2 = reinterpret_cast<uint32_t*>(p);
+    p += b_nc;
+    a.norm1 = norm1;
+    a.norm2 = norm2;
+    a.idx = reinterpret_cast<uint32_t*>(p), p += b_out;
+    a.dist = reinterpret_cast<uint32_t*>(p), p += b_out;
+    a.idx2 = reinterpret_cast<uint32_t*>(p), p += b_out;
+    a.dist2 = reinterpret_cast<uint32_t*>(p), p += b_out;
+    if (splits > 1) {
+        a.p_idx = reinterpret_cast<uint32_t*>(p), p += b_part;
+        a.p_dist = reinterpret_cast<uint32_t*>(p), p += b_part;
+        a.p_idx2 = reinterpret_cast<uint32_t*>(p), p += b_part;
+        a.p_dist2 = reinterpret_cast<uint32_t*>(p), p += b_part;
+    } else {
+        a.p_idx = a.idx;
+        a.p_dist = a.dist;
+        a.p_idx2 = a.idx2;
+        a.p_dist2 = a.dist2;
+    }
+    a.n1 = (uint32_t)nr;
+    a.n2 = (uint32_t)nc;
+    a.splits = splits;
+    a.cols = cols;
+    g.row_terms = reverse ? t2 : t1;
+    g.col_terms = reverse ? t1 : t2;
+    g.T = sq_threshold;
+    g.kind = kind;
+    g.reverse = reverse;
+    MatchGeoModel mdl;
+    for (int k = 0; k < 9; ++k) mdl.h[k] = model[k];
+
+    e = hipEventCreate(&ev0);
+    if (e == hipSuccess) e = hipEventCreate(&ev1);
+    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(a.d1), dr, nr * dim, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(a.d2), dc, nc * dim, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dp1, p1, n1 * 2 * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dp2, p2, n2 * 2 * sizeof(double), hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipEventRecord(ev0, stream);
+    if (e == hipSuccess) {
+        const uint32_t nb = (uint32_t)((n1 + n2 + kMatchThreads - 1) / kMatchThreads);
+        hipLaunchKernelGGL(k_match_norms, dim3(nb), dim3(kMatchThreads), 0, stream, a.d1, a.n1, a.d2, a.n2, dim,
+                           norm1, norm2);
+        hipLaunchKernelGGL(k_match_geo_terms, dim3(nb), dim3(kMatchThreads), 0, stream, dp1, (uint32_t)n1, dp2,
+                           (uint32_t)n2, mdl, kind, t1, t2);
+        kLaunchGeo[dim / 32 - 1](g, (uint32_t)(row_blocks * splits), stream);
+        if (splits > 1)
+            hipLaunchKernelGGL(k_match_merge, dim3((uint32_t)((nr + kMatchThreads - 1) / kMatchThreads)),
+                               dim3(kMatchThreads), 0, stream, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipEventRecord(ev1, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(idx, a.idx, nr * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dist, a.dist, nr * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(idx2, a.idx2, nr * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(dist2, a.dist2, nr * 4, hipMemcpyDeviceToHost, stream);
     if (e == hipSuccess) e = hipStreamSynchronize(stream);
     if (e == hipSuccess && ms_kernel) {
         float ms = 0.f;

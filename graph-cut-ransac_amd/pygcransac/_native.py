@@ -262,6 +262,11 @@ def _load():
     # descriptor matching (csrc/match.h): uint8 descriptors in, idx / dist / idx2 / dist2 (uint32) out
     L.gcr_match_descriptors.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, vp, vp, vp, vp, dp]
     L.gcr_host_match_descriptors.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_int, vp, vp, vp, vp]
+    # guided matching (csrc/match_geo.h): positions, kind, model, squared bound, direction
+    L.gcr_match_descriptors_guided.argtypes = [vp, vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, vp,
+                                               C.c_double, C.c_int, vp, vp, vp, vp, dp]
+    L.gcr_host_match_descriptors_guided.argtypes = [vp, C.c_size_t, vp, vp, C.c_size_t, vp, C.c_uint32, C.c_int, vp,
+                                                    C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gcr_match_tiling.argtypes = [u32p]
     L.gcr_match_tiling.restype = None
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,

@@ -12,6 +12,10 @@ neighbour matching of uint8 (SIFT-style) descriptors on the GPU's int8 matrix
 cores (gcr_match_descriptors, csrc/match.h), with the ratio test and the
 mutual check.  `quantize_descriptors` brings float descriptors to uint8 and
 `correspondences_from_matches` builds the estimators' rows from the matches.
+`match_descriptors_guided` is the matcher's second run, after the estimator:
+the same search among the pairs that agree with the estimated homography or
+fundamental matrix (gcr_match_descriptors_guided, csrc/match_geo.h);
+`fundamental_from_essential` brings an essential matrix to that form.
 """
 from __future__ import annotations
 
@@ -19,7 +23,7 @@ import numpy as np
 
 __all__ = ["scale_features_from_sift", "orientation_features_from_sift", "keypoints_to_array", "perspective_warp",
            "warp_geometry", "BORDER_CONSTANT", "BORDER_REPLICATE", "match_descriptors", "quantize_descriptors",
-           "correspondences_from_matches"]
+           "correspondences_from_matches", "match_descriptors_guided", "fundamental_from_essential"]
 
 # OpenCV's border codes (cv2.BORDER_CONSTANT = 0, cv2.BORDER_REPLICATE = 1)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
@@ -213,6 +217,135 @@ def match_descriptors(desc1, desc2, ratio=0.8, mutual=True, *, backend="gpu", de
     rows = np.nonzero(keep)[0]
     matches = np.stack([rows.astype(np.int64), idx[rows].astype(np.int64)], axis=1)
     return matches, ratios[rows]
+
+
+def _positions(kp, name):
+    """(N, 2) contiguous float64 (x, y) from keypoints (keypoints_to_array's columns 0 and 1) or an (N, 2) array."""
+    if isinstance(kp, np.ndarray) and kp.ndim == 2 and kp.shape[1] == 2:
+        a = np.asarray(kp, dtype=np.float64)
+    else:
+        a = keypoints_to_array(kp)[:, :2]
+    if not np.isfinite(a).all():
+        raise ValueError(f"{name} has a non-finite position")
+    return np.ascontiguousarray(a)
+
+
+_GUIDED_KINDS = {"homography": 3, "fundamental": 4}     # GCR_SOLVER_HOMOGRAPHY4, GCR_SOLVER_FUNDAMENTAL7
+
+
+def _nearest_two_guided(d1, p1, d2, p2, kind, model, sq_threshold, reverse, backend, device):
+    """idx, dist, idx2, dist2 (uint32): one per row of d1, or of d2 with reverse=1."""
+    from . import _native as N
+
+    n = d2.shape[0] if reverse else d1.shape[0]
+    out = [np.empty(n, dtype=np.uint32) for _ in range(4)]
+    ptrs = [o.ctypes.data for o in out]
+    args = (d1.ctypes.data, d1.shape[0], p1.ctypes.data, d2.ctypes.data, d2.shape[0], p2.ctypes.data, d1.shape[1],
+            kind, model.ctypes.data, float(sq_threshold), int(reverse))
+    if backend == "host":
+        import os
+
+        threads = max(1, min(16, os.cpu_count() or 1))
+        N.check(N.lib.gcr_host_match_descriptors_guided(*args, threads, *ptrs))
+    else:
+        N.check(N.lib.gcr_match_descriptors_guided(N.context(device), *args, *ptrs, None))
+    return out
+
+
+def match_descriptors_guided(desc1, desc2, kp1, kp2, model, kind, threshold, ratio=None, mutual=True,
+                             max_distance=None, *, backend="gpu", device=None):
+    """Guided matching, the matcher's second run once a model is known: keypoint
+    j of image 2 competes for keypoint i of image 1 only if the pair agrees
+    with ``model``.  This recovers the correspondences that the ratio test and
+    the mutual check of ``match_descriptors`` had to drop as ambiguous.
+
+    ``desc1`` / ``desc2`` as for ``match_descriptors``.  ``kp1`` / ``kp2`` are
+    read as by ``keypoints_to_array`` (columns 0 and 1: x, y); an (N, 2) array
+    of positions is accepted too; one keypoint per descriptor row.  ``model``
+    is 3 x 3 and ``kind`` says what it is: ``"homography"`` (image 1 to image
+    2; the residual is the squared transfer error in image 2) or
+    ``"fundamental"`` (x2^T F x1 = 0; the squared Sampson distance) -- the
+    residuals of findHomography and findFundamentalMatrix.  An essential
+    matrix goes through ``fundamental_from_essential`` first.  The pair (i, j)
+    is admissible iff its residual is <= ``threshold * threshold`` in float64;
+    ``threshold`` is in pixels, finite and > 0.  The estimators' own inlier
+    mask uses the wider bound ``(2.25 * t) * t`` for their ``threshold`` t (1.5 t
+    in pixels), so ``threshold = 1.5 * t`` admits the pairs that the estimator
+    would call inliers of ``model`` (up to the rounding of the two bounds).
+
+    Among the admissible candidates the search is ``match_descriptors``'s:
+    exact squared descriptor distances, the lower index on a tie.
+    ``mutual=True`` (a second search from image 2's side over the same
+    admissible pairs) keeps (i, j) iff each is the other's first admissible
+    neighbour.  ``ratio`` defaults to None: the geometry does the
+    disambiguation.  When given, ``match_descriptors``'s float64 rule applies
+    to the best and the second-best ADMISSIBLE candidate; a row with a single
+    admissible candidate passes, because nothing competes with it.
+    ``max_distance`` (optional) keeps a pair only if its squared descriptor
+    distance is <= max_distance; under a homography, where a false keypoint
+    often has one random admissible candidate, it is the only protection.
+    A row without an admissible candidate gives no match.
+
+    Returns ``(matches, ratios)`` as ``match_descriptors``: (M, 2) int64 rows
+    (i, j) sorted by i and (M,) float64 sqrt(dist / dist2), 1.0 for 0 / 0 and
+    where there is no second admissible neighbour."""
+    d1 = _as_descriptors(desc1, "desc1")
+    d2 = _as_descriptors(desc2, "desc2")
+    if d1.shape[1] != d2.shape[1]:
+        raise ValueError(f"desc1 and desc2 differ in dimension: {d1.shape[1]} and {d2.shape[1]}")
+    if d1.shape[1] % 32 or not 32 <= d1.shape[1] <= 512:
+        raise ValueError(f"the descriptor dimension must be a multiple of 32 in 32..512, got {d1.shape[1]}")
+    if d1.shape[0] == 0 or d2.shape[0] == 0:
+        raise ValueError("desc1 and desc2 need at least one row each")
+    if backend not in ("gpu", "host"):
+        raise ValueError(f"backend must be 'gpu' or 'host', got {backend!r}")
+    if kind not in _GUIDED_KINDS:
+        raise ValueError(f"kind must be 'homography' or 'fundamental', got {kind!r}")
+    p1, p2 = _positions(kp1, "kp1"), _positions(kp2, "kp2")
+    if len(p1) != len(d1) or len(p2) != len(d2):
+        raise ValueError(f"one keypoint per descriptor: kp1 has {len(p1)} rows for {len(d1)} descriptors, "
+                         f"kp2 {len(p2)} for {len(d2)}")
+    m = np.asarray(model, dtype=np.float64)
+    if m.shape != (3, 3) or not np.isfinite(m).all():
+        raise ValueError("model must be a finite 3 x 3 matrix")
+    m = np.ascontiguousarray(m)
+    if not (np.isfinite(threshold) and threshold > 0):
+        raise ValueError("threshold must be a finite number of pixels > 0")
+    if ratio is not None and not (np.isfinite(ratio) and ratio > 0):
+        raise ValueError("ratio must be None or a finite number > 0")
+    if max_distance is not None and not max_distance >= 0:
+        raise ValueError("max_distance must be None or a number >= 0")
+    T = float(threshold) * float(threshold)
+    code = _GUIDED_KINDS[kind]
+    idx, dist, idx2, dist2 = _nearest_two_guided(d1, p1, d2, p2, code, m, T, 0, backend, device)
+    found = idx != 0xFFFFFFFF
+    none = idx2 == 0xFFFFFFFF
+    fd, fd2 = dist.astype(np.float64), dist2.astype(np.float64)
+    ratios = np.ones(len(idx), dtype=np.float64)
+    ok = found & ~none & (fd2 > 0)
+    ratios[ok] = np.sqrt(fd[ok] / fd2[ok])
+    keep = found.copy()
+    if ratio is not None:
+        keep &= none | (fd < (float(ratio) * float(ratio)) * fd2)
+    if max_distance is not None:
+        keep &= fd <= float(max_distance)
+    if mutual:
+        back = _nearest_two_guided(d1, p1, d2, p2, code, m, T, 1, backend, device)[0]
+        rows = np.nonzero(keep)[0]
+        keep[rows] = back[idx[rows]] == rows.astype(np.uint32)
+    rows = np.nonzero(keep)[0]
+    matches = np.stack([rows.astype(np.int64), idx[rows].astype(np.int64)], axis=1)
+    return matches, ratios[rows]
+
+
+def fundamental_from_essential(E, K1, K2) -> np.ndarray:
+    """F = K2^-T E K1^-1: the fundamental matrix of the pixel coordinates from
+    an essential matrix (findEssentialMatrix, findGravityEssentialMatrix) and
+    the two calibration matrices, for ``match_descriptors_guided``."""
+    E, K1, K2 = (np.asarray(a, dtype=np.float64) for a in (E, K1, K2))
+    if E.shape != (3, 3) or K1.shape != (3, 3) or K2.shape != (3, 3):
+        raise ValueError("E, K1 and K2 must be 3 x 3")
+    return np.linalg.inv(K2).T @ E @ np.linalg.inv(K1)
 
 
 def correspondences_from_matches(kp1, kp2, matches, sift=False) -> np.ndarray:

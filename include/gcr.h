@@ -754,6 +754,33 @@ int gcr_match_descriptors(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const uint
  * rows of d1 only and does not change the result */
 int gcr_host_match_descriptors(const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim, int threads,
                                uint32_t* idx_out, uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out);
+/* Guided matching (csrc/match_geo.h is the definition): the same 2-nearest-
+ * neighbour search among the pairs a two-view model admits.  p1 (n1 x 2) and
+ * p2 (n2 x 2) are the keypoint positions, row-major doubles (x, y); kind is
+ * GCR_SOLVER_HOMOGRAPHY4 (squared transfer error of p1 -> p2 under the
+ * homography `model`) or GCR_SOLVER_FUNDAMENTAL7 (squared Sampson distance
+ * under the fundamental matrix `model`), the estimators' own residuals;
+ * model is 9 doubles, row-major.  The pair (i, j) of row i of image 1 and row
+ * j of image 2 is admissible iff its residual <= sq_threshold in fp64 (a NaN
+ * residual never is; sq_threshold = +inf admits every other pair).
+ * reverse = 0: for every i the first two admissible j in the order
+ * (d(i, j), j), n1 values per output.  reverse = 1: for every j the first two
+ * admissible i in the order (d(i, j), i), n2 values per output.  0xFFFFFFFF in
+ * idx_out and dist_out where a row has no admissible candidate, in idx2_out
+ * and dist2_out where it has one.  The device result equals
+ * gcr_host_match_descriptors_guided's bit for bit.  Errors as
+ * gcr_match_descriptors, and: NULL p1, p2 or model, another kind, a NaN or
+ * negative sq_threshold, a non-finite model entry, reverse not 0 or 1. */
+int gcr_match_descriptors_guided(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const double* p1, const uint8_t* d2,
+                                 size_t n2, const double* p2, uint32_t dim, int kind, const double* model,
+                                 double sq_threshold, int reverse, uint32_t* idx_out, uint32_t* dist_out,
+                                 uint32_t* idx2_out, uint32_t* dist2_out, double* ms_kernel_out);
+/* host-only: the same by plain loops; `threads` (clamped to 1..64) splits the
+ * result rows only and does not change the result */
+int gcr_host_match_descriptors_guided(const uint8_t* d1, size_t n1, const double* p1, const uint8_t* d2, size_t n2,
+                                      const double* p2, uint32_t dim, int kind, const double* model,
+                                      double sq_threshold, int reverse, int threads, uint32_t* idx_out,
+                                      uint32_t* dist_out, uint32_t* idx2_out, uint32_t* dist2_out);
 /* the matcher kernels' tiling, for tests at its edges: out[0] = rows of d1 per
  * workgroup, out[1] = rows of d2 (columns) per step, out[2] = the least
  * columns per split the planner chooses */

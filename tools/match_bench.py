@@ -16,6 +16,15 @@ uint8 descriptors of dim 128 (uniform random bytes, seeded).
      mutual=False) + findHomography(sampler=1, probabilities=-ratios) beside
      the estimator call alone, the median of --calls calls each, alternating
 
+With --guided only the guided matcher runs (gcr_match_descriptors_guided) on
+problem_match(n, 0.4 n)'s keypoints and descriptors at a 3 px bound: under
+H_GT and under F = [e']x H_GT, forward and mutual (forward + reverse), kernels
+and whole calls, interleaved call by call with the unguided matcher on the
+same descriptors; whether the host twin agrees bit for bit; the admissible
+share of the pairs, and the share of the kernel's 32 x 32 tiles and of its
+128-row x 64-column steps without an admissible pair (numpy, from the
+definition), which the kernel skips.
+
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -37,6 +46,8 @@ ap.add_argument("--threads", type=int, default=16, help="host twin's threads")
 ap.add_argument("--host-runs", type=int, default=3)
 ap.add_argument("--splits", default="0,1,2,4,7,16", help="column splits to time (GCR_MATCH_SPLIT), 0 = the planner's")
 ap.add_argument("--no-pipeline", action="store_true")
+ap.add_argument("--guided", action="store_true", help="the guided matcher's legs only")
+ap.add_argument("--threshold", type=float, default=3.0, help="guided: the bound in pixels")
 args = ap.parse_args()
 
 sys.path.insert(0, args.pkg)
@@ -69,6 +80,102 @@ def gpu_call(res, ms):
                                         *[r.ctypes.data for r in res], C.byref(ms)))
     return (time.perf_counter() - t0) * 1e3           # the call ends in a stream synchronisation
 
+
+# ---- guided mode ---------------------------------------------------------------
+def guided_mode():
+    kp1, e1, kp2, e2, pairs, Hgt = S.problem_match(n, int(0.4 * n), seed=SEED, dim=dim)
+    p1, p2 = np.ascontiguousarray(kp1[:, :2]), np.ascontiguousarray(kp2[:, :2])
+    e = (2.0 * S.IMG_W, S.IMG_H / 2.0, 1.0)
+    skew = np.array([[0.0, -e[2], e[1]], [e[2], 0.0, -e[0]], [-e[1], e[0], 0.0]])
+    models = {"H": (3, np.ascontiguousarray(Hgt)), "F": (4, np.ascontiguousarray(skew @ Hgt))}
+    T = args.threshold * args.threshold
+    ms = C.c_double()
+
+    def unguided(res):
+        t0 = time.perf_counter()
+        N.check(N.lib.gcr_match_descriptors(ctx, e1.ctypes.data, n, e2.ctypes.data, n, dim,
+                                            *[r.ctypes.data for r in res], C.byref(ms)))
+        return (time.perf_counter() - t0) * 1e3, ms.value
+
+    def guided(kind, model, reverse, res, host=False):
+        a = (e1.ctypes.data, n, p1.ctypes.data, e2.ctypes.data, n, p2.ctypes.data, dim, kind, model.ctypes.data, T,
+             reverse)
+        t0 = time.perf_counter()
+        if host:
+            N.check(N.lib.gcr_host_match_descriptors_guided(*a, args.threads, *[r.ctypes.data for r in res]))
+        else:
+            N.check(N.lib.gcr_match_descriptors_guided(ctx, *a, *[r.ctypes.data for r in res], C.byref(ms)))
+        return (time.perf_counter() - t0) * 1e3, ms.value
+
+    names = ["unguided"] + [f"{k}_{d}" for k in models for d in ("forward", "reverse")]
+    res = {name: [np.empty(n, dtype=np.uint32) for _ in range(4)] for name in names}
+    acc = {name: ([], []) for name in names}
+    for k in range(-1, args.calls):                   # call -1 warms up; the legs alternate call by call
+        for name in names:
+            if name == "unguided":
+                whole, kern = unguided(res[name])
+            else:
+                kind, model = models[name[0]]
+                whole, kern = guided(kind, model, int(name.endswith("reverse")), res[name])
+            if k >= 0:
+                acc[name][0].append(kern)
+                acc[name][1].append(whole)
+    g = {name: {"kernel": quart(v[0]), "call": quart(v[1])} for name, v in acc.items()}
+    for k in models:
+        g[f"{k}_mutual"] = {"kernel": quart([a + b for a, b in zip(acc[f"{k}_forward"][0], acc[f"{k}_reverse"][0])]),
+                            "call": quart([a + b for a, b in zip(acc[f"{k}_forward"][1], acc[f"{k}_reverse"][1])])}
+    truth = set(map(tuple, pairs.tolist()))
+    for k, (kind, model) in models.items():
+        for d in ("forward", "reverse"):
+            host = [np.empty(n, dtype=np.uint32) for _ in range(4)]
+            host_ms, _ = guided(kind, model, int(d == "reverse"), host, host=True)
+            g[f"{k}_{d}"]["host_twin_ms"] = round(host_ms, 2)
+            g[f"{k}_{d}"]["equals_host_twin_bitwise"] = all(np.array_equal(a, b)
+                                                            for a, b in zip(host, res[f"{k}_{d}"]))
+        m, _ = F.match_descriptors_guided(e1, e2, kp1, kp2, model, {"H": "homography", "F": "fundamental"}[k],
+                                          args.threshold)
+        g[f"{k}_mutual"]["matches"] = len(m)
+        g[f"{k}_mutual"]["truth_pairs_found"] = len(set(map(tuple, m.tolist())) & truth)
+    # the admissible share and what the kernel skips, from the definition (forward: rows are image 1)
+    x2, y2 = p2[:, 0][None, :], p2[:, 1][None, :]
+    ct = (n + 31) // 32
+    for k, (kind, model) in models.items():
+        h = model.reshape(9)
+        adm_pairs = tiles = empty_tiles = steps = empty_steps = 0
+        for lo in range(0, n, 128):
+            x1, y1 = p1[lo:lo + 128, 0][:, None], p1[lo:lo + 128, 1][:, None]
+            if kind == 3:
+                w = (h[6] * x1 + h[7] * y1) + h[8]
+                du = ((h[0] * x1 + h[1] * y1) + h[2]) / w - x2
+                dv = ((h[3] * x1 + h[4] * y1) + h[5]) / w - y2
+                r = du * du + dv * dv
+            else:
+                fx0, fx1 = (h[0] * x1 + h[1] * y1) + h[2], (h[3] * x1 + h[4] * y1) + h[5]
+                fx2 = (h[6] * x1 + h[7] * y1) + h[8]
+                ft0, ft1 = (h[0] * x2 + h[3] * y2) + h[6], (h[1] * x2 + h[4] * y2) + h[7]
+                num = (x2 * fx0 + y2 * fx1) + fx2
+                r = (num * num) / (((fx0 * fx0 + fx1 * fx1) + ft0 * ft0) + ft1 * ft1)
+            adm = np.zeros((128, ct * 32), dtype=bool)
+            adm[:r.shape[0], :n] = r <= T
+            adm_pairs += int(adm.sum())
+            t = adm.reshape(4, 32, ct, 32).any(axis=(1, 3))[:(r.shape[0] + 31) // 32]
+            tiles += t.size
+            empty_tiles += int((~t).sum())
+            st = adm.any(axis=0)
+            st = np.concatenate([st, np.zeros(-len(st) % 64, dtype=bool)]).reshape(-1, 64).any(axis=1)
+            steps += st.size
+            empty_steps += int((~st).sum())
+        g[f"{k}_forward"].update({"admissible_share": adm_pairs / (n * n), "tiles": tiles,
+                                  "tile_skip_rate": round(empty_tiles / tiles, 6), "steps": steps,
+                                  "step_skip_rate": round(empty_steps / steps, 6)})
+    out["guided"] = g
+    out["threshold_px"] = args.threshold
+    print(json.dumps(out))
+
+
+if args.guided:
+    guided_mode()
+    sys.exit(0)
 
 # ---- leg 1 ---------------------------------------------------------------------
 gpu = [np.empty(n, dtype=np.uint32) for _ in range(4)]
