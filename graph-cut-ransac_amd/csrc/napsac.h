@@ -37,6 +37,18 @@
 //           without i0).  The sample is i0, then these rows in draw order.
 //           Every attempt of a slot shares l_min and draws its own i0.
 //
+// For the essential-matrix estimators the layers lie over the PIXEL rows, as
+// the graph cut's neighbourhood grid does, not over the K-normalised rows the
+// solver reads.  Local optimisation's inner samples stay the uniform
+// sampler's on its own stream (kStreamLO).
+//
+// Pinned: the oracle (oracle/gcr_oracle.cpp) restates this block without
+// including this header, its layers grouped by its own grid index;
+// tests/test_oracle_samplers.py holds layers and samples to the host entries
+// bit for bit, and tests/test_gpu_oracle_samplers.py compares whole NAPSAC
+// runs of all five correspondence estimators with the oracle's run loop
+// bitwise.
+//
 // Only the sampler changes: the stop is the reference's uniform bound.  From
 // slot T on every sample is the uniform sampler's, which is what that bound
 // describes.  The engine applies the same bound before T as well, where the

@@ -26,11 +26,19 @@
 //           last position.  Past it (t > g[N]): sample_distinct over N with m
 //           indices, the uniform sampler's own bits for that slot.
 //
-// Only the sampler changes: the stop is the reference's uniform bound (valid,
-// since the sampler becomes the uniform one).  PROSAC's own non-randomness /
-// maximality stop is opt-in (GCR_FLAG_PROSAC_STOP) and defined in
-// prosac_stop.h; it reads this table's g[n] as the number of slots whose pool
-// lies within the first n rows.
+// Only the main loop's sampler changes.  Local optimisation's inner samples
+// stay the uniform sampler's on its own stream (kStreamLO), drawn from the
+// graph cut's inliers whatever their rank.  The stop is the reference's
+// uniform bound (valid, since the sampler becomes the uniform one).  PROSAC's
+// own non-randomness / maximality stop is opt-in (GCR_FLAG_PROSAC_STOP) and
+// defined in prosac_stop.h; it reads this table's g[n] as the number of slots
+// whose pool lies within the first n rows.
+//
+// Pinned: the oracle (oracle/gcr_oracle.cpp) restates this block without
+// including this header; tests/test_oracle_samplers.py holds the restatement
+// to the host entries bit for bit, and tests/test_gpu_oracle_samplers.py
+// compares whole PROSAC runs of all five correspondence estimators with the
+// oracle's run loop bitwise, through the Python wrapper's sort and unsort.
 //
 // The generators do not search g in global memory per attempt.  A workgroup
 // covers at most kProsacWindow consecutive slots and g is strictly increasing,

@@ -41,6 +41,16 @@
 //            (double)I* / (double)n* in place of I / N, otherwise line for
 //            line the same (pow, log(1 - q), the epsilon guard, ceil).
 //
+//   when     wherever the uniform run updates max_iteration, with the model
+//            that is the best at that point: a generated hypothesis that
+//            becomes the best takes its own (I*, n*), and after a local
+//            optimisation the best it leaves (the LO model if it won, else the
+//            model that went in) takes its own again.  A hypothesis that does
+//            not become the best never moves the stop.  The oracle's run loop
+//            (oracle/gcr_oracle.cpp, stopNumber) states this independently, and
+//            tests/test_gpu_oracle_samplers.py compares whole flagged runs
+//            with it bitwise.
+//
 // With n* = N the formula is the uniform stop bit for bit, and (I_N, N) is
 // always a candidate, so I* / n* >= I_N / N: the flag can only lower
 // max_iteration, never raise it.  The result is a function of the model and

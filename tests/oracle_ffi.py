@@ -39,6 +39,16 @@ class OracleStats(C.Structure):
     ]
 
 
+class OracleSampling(C.Structure):
+    """mode 0: uniform or guided (by weights), 1: PROSAC, 2: NAPSAC; star_i /
+    star_n: (I*, n*) of the last stop update of a prosac_stop run (out)."""
+    _fields_ = [
+        ("mode", C.c_int32), ("prosac_stop", C.c_int32), ("prosac_convergence", C.c_uint64),
+        ("napsac_iterations", C.c_uint64), ("napsac_extent", C.c_double * 4),
+        ("star_i", C.c_uint64), ("star_n", C.c_uint64),
+    ]
+
+
 _lib = None
 
 
@@ -446,10 +456,23 @@ def _calib_lib():
     L = lib()
     if not _calib_ready:
         pp, sp = C.POINTER(OracleParams), C.POINTER(OracleStats)
+        smp = C.POINTER(OracleSampling)
         L.oracle_find_calibrated.argtypes = [_DP, _DP, C.c_size_t, pp, C.c_uint32, C.c_uint32, MINIMAL_FN, FIT_FN,
-                                             C.c_void_p, _DP, C.c_int, _U8P, _DP, sp]
-        L.oracle_find_homography_guided.argtypes = [_DP, C.c_size_t, pp, _DP, C.c_int, _U8P, _DP, sp]
+                                             C.c_void_p, _DP, C.c_int, _U8P, _DP, sp, smp]
+        L.oracle_find_homography_guided.argtypes = [_DP, C.c_size_t, pp, _DP, C.c_int, _U8P, _DP, sp, smp]
         L.oracle_find_fundamental_guided.argtypes = L.oracle_find_homography_guided.argtypes
+        L.oracle_find_homography_sift.argtypes = [_DP, C.c_size_t, pp, C.c_uint32, MINIMAL_FN, C.c_void_p, _DP,
+                                                  C.c_int, _U8P, _DP, sp, smp]
+        L.oracle_prosac_growth.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, _U64P]
+        L.oracle_sample_prosac.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint64,
+                                           C.c_uint32, C.c_uint64, _U64P, _U64P]
+        L.oracle_prosac_stop_tables.argtypes = [C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, _U32P, _DP]
+        L.oracle_prosac_stop_choice.argtypes = [_U8P, C.c_uint64, C.c_uint32, C.c_uint64, C.c_double, _U64P, _U64P]
+        L.oracle_prosac_stop_number.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_double]
+        L.oracle_prosac_stop_number.restype = C.c_uint64
+        L.oracle_napsac_layers.argtypes = [_DP, C.c_uint64, _DP, _U32P, _U32P, _U32P, _U32P]
+        L.oracle_samples_napsac.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _DP, C.c_uint64,
+                                            C.c_uint32, _DP, C.c_uint64, _U32P]
         L.oracle_sample_guided.argtypes = [C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, _DP,
                                            C.c_uint64, C.c_uint32, _U64P]
         L.oracle_guided_pick.argtypes = [_DP, C.c_uint64, C.c_uint64]
@@ -499,6 +522,37 @@ def _weights(weights, n):
     return w
 
 
+SAMPLING_KEYS = ("sampler", "prosac_convergence", "prosac_stop", "napsac_iterations", "napsac_extent")
+
+
+def _sampling(kw):
+    """(kw without the sampler arguments, OracleSampling or None).  sampler: 0
+    (uniform, or guided by weights), 1 (PROSAC: the rows are in quality order)
+    or 2 (NAPSAC: napsac_extent = (w1, h1, w2, h2), napsac_iterations = T)."""
+    kw = dict(kw)
+    got = {k: kw.pop(k) for k in SAMPLING_KEYS if k in kw}
+    mode = int(got.get("sampler", 0) or 0)
+    if mode == 0 and not got.get("prosac_stop"):
+        return kw, None
+    s = OracleSampling()
+    s.mode = mode
+    s.prosac_stop = int(bool(got.get("prosac_stop", False)))
+    s.prosac_convergence = int(got.get("prosac_convergence", 100000))
+    if mode == 2:
+        s.napsac_iterations = int(got["napsac_iterations"])
+        s.napsac_extent[:] = [float(v) for v in got["napsac_extent"]]
+    return kw, s
+
+
+def _result(r, mask, M, st, sampling, **more):
+    if r < 0:
+        raise RuntimeError("oracle failed")
+    out = dict(num_inliers=r, mask=mask.astype(bool), H=M.reshape(3, 3), stats=_stats_dict(st), **more)
+    if sampling is not None and sampling.prosac_stop:
+        out["prosac_star"] = (int(sampling.star_i), int(sampling.star_n))
+    return out
+
+
 def _guided_corr(entry, corr, thr, weights, guided_stop, kw):
     c = _f64(corr)
     n = c.shape[0]
@@ -506,23 +560,117 @@ def _guided_corr(entry, corr, thr, weights, guided_stop, kw):
     mask = np.zeros(n, dtype=np.uint8)
     M = np.zeros(9)
     st = OracleStats()
+    kw, smp = _sampling(kw)
     p = params(thr, **kw)
     r = entry(_dp(c), n, C.byref(p), None if w is None else _dp(w), int(bool(guided_stop)),
-              mask.ctypes.data_as(_U8P), _dp(M), C.byref(st))
-    if r < 0:
-        raise RuntimeError("oracle failed")
-    return dict(num_inliers=r, mask=mask.astype(bool), H=M.reshape(3, 3), stats=_stats_dict(st))
+              mask.ctypes.data_as(_U8P), _dp(M), C.byref(st), None if smp is None else C.byref(smp))
+    return _result(r, mask, M, st, smp)
 
 
-def find_homography_guided(corr, thr, weights, guided_stop=False, **kw):
+def find_homography_guided(corr, thr, weights=None, guided_stop=False, **kw):
     """find_homography with the main loop's samples drawn by the guided
     sampler (weights None: the uniform run) and, with guided_stop, the stop on
-    the inlier mass."""
+    the inlier mass; or, by the sampler arguments of _sampling, by PROSAC
+    (prosac_stop: its own stop) or NAPSAC."""
     return _guided_corr(_calib_lib().oracle_find_homography_guided, corr, thr, weights, guided_stop, kw)
 
 
-def find_fundamental_guided(corr, thr, weights, guided_stop=False, **kw):
+def find_fundamental_guided(corr, thr, weights=None, guided_stop=False, **kw):
     return _guided_corr(_calib_lib().oracle_find_fundamental_guided, corr, thr, weights, guided_stop, kw)
+
+
+def find_homography_sift(corr8, thr, weights=None, guided_stop=False, **kw):
+    """findHomographySIFT through the oracle's run loop: the 2-point solver
+    reaches it as a callback over gcr_host_solve_s2 (the SIFT columns stay
+    here; the callback gets the run's own x1, y1, x2, y2 rows), everything
+    else is the oracle's homography solver."""
+    from pygcransac import _native as N
+
+    c8 = _f64(corr8)
+    c = np.ascontiguousarray(c8[:, :4])
+    sift = np.ascontiguousarray(c8[:, 4:8])
+    n = c.shape[0]
+    cnt = C.c_uint32()
+
+    def minimal(user, rows, nrows, idx, out):
+        rc = N.lib.gcr_host_solve_s2(C.cast(rows, C.c_void_p), sift.ctypes.data, nrows, C.cast(idx, C.c_void_p),
+                                     C.cast(out, C.c_void_p), C.byref(cnt))
+        return int(cnt.value) if rc == 0 else -1
+
+    w = _weights(weights, n)
+    mask = np.zeros(n, dtype=np.uint8)
+    M = np.zeros(9)
+    st = OracleStats()
+    kw, smp = _sampling(kw)
+    p = params(thr, **kw)
+    cb = MINIMAL_FN(_guarded(minimal))
+    r = _calib_lib().oracle_find_homography_sift(_dp(c), n, C.byref(p), 3, cb, None, None if w is None else _dp(w),
+                                                 int(bool(guided_stop)), mask.ctypes.data_as(_U8P), _dp(M),
+                                                 C.byref(st), None if smp is None else C.byref(smp))
+    return _result(r, mask, M, st, smp)
+
+
+# ---- the sampler restatements alone ---------------------------------------------
+def prosac_growth(n, m, convergence):
+    g = np.zeros(n + 1, dtype=np.uint64)
+    if _calib_lib().oracle_prosac_growth(n, m, convergence, g.ctypes.data_as(_U64P)) != 0:
+        raise ValueError("need 1 <= m <= n")
+    return g
+
+
+def sample_prosac(seed, slot, attempt, n, m, convergence):
+    """(indices or None when the budget ran out, the slot's pool; 0 = uniform phase)"""
+    out = np.zeros(m, dtype=np.uint64)
+    pool = C.c_uint64()
+    r = _calib_lib().oracle_sample_prosac(seed, slot, attempt, 0, 0, n, m, convergence, out.ctypes.data_as(_U64P),
+                                          C.byref(pool))
+    if r == -2:
+        raise ValueError("need 1 <= m <= n")
+    return (out if r == 0 else None), int(pool.value)
+
+
+def prosac_stop_tables(n, m, convergence, confidence):
+    imin = np.zeros(n + 1, dtype=np.uint32)
+    qmin = np.zeros(n + 1)
+    if _calib_lib().oracle_prosac_stop_tables(n, m, convergence, confidence, imin.ctypes.data_as(_U32P),
+                                              _dp(qmin)) != 0:
+        raise ValueError("need 1 <= m <= n")
+    return imin, qmin
+
+
+def prosac_stop_choice(mask, m, convergence, confidence):
+    """(I*, n*) of the mask in row order"""
+    mk = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+    bi, bn = C.c_uint64(), C.c_uint64()
+    if _calib_lib().oracle_prosac_stop_choice(mk.ctypes.data_as(_U8P), len(mk), m, convergence, confidence,
+                                              C.byref(bi), C.byref(bn)) != 0:
+        raise ValueError("need 1 <= m <= n")
+    return int(bi.value), int(bn.value)
+
+
+def prosac_stop_number(best_i, best_n, m, confidence):
+    return int(_calib_lib().oracle_prosac_stop_number(best_i, best_n, m, confidence))
+
+
+def napsac_layers(rows, extent):
+    """per layer (members, start, count, pos), napsac_cases.host_layers' layout"""
+    r = _f64(rows)
+    n = len(r)
+    e = _f64(extent)
+    mem, start, count, pos = (np.zeros((4, n), dtype=np.uint32) for _ in range(4))
+    _calib_lib().oracle_napsac_layers(_dp(r), n, _dp(e), *[a.ctypes.data_as(_U32P) for a in (mem, start, count, pos)])
+    return [(mem[l], start[l], count[l], pos[l]) for l in range(4)]
+
+
+def samples_napsac(seed, slot0, nslots, attempt, rows, m, extent, T):
+    """(nslots, m) uint32, all-ones rows where the budget ran out"""
+    r = _f64(rows)
+    e = _f64(extent)
+    out = np.zeros((nslots, m), dtype=np.uint32)
+    if _calib_lib().oracle_samples_napsac(seed, slot0, nslots, attempt, _dp(r), len(r), m, _dp(e), T,
+                                          out.ctypes.data_as(_U32P)) != 0:
+        raise ValueError("need 1 <= m <= n and T >= 1")
+    return out
 
 
 def _guarded(fn):
@@ -561,15 +709,14 @@ def _find_calibrated(corr, K1, K2, thr, m, per, minimal, fit, weights, guided_st
     mask = np.zeros(n, dtype=np.uint8)
     E = np.zeros(9)
     st = OracleStats()
+    kw, smp = _sampling(kw)
     p = params(thr_n.value, **kw)
     cb_min, cb_fit = MINIMAL_FN(_guarded(minimal)), FIT_FN(_guarded(fit))
     r = _calib_lib().oracle_find_calibrated(_dp(norm), _dp(c), n, C.byref(p), m, per, cb_min, cb_fit, None,
                                             None if w is None else _dp(w), int(bool(guided_stop)),
-                                            mask.ctypes.data_as(_U8P), _dp(E), C.byref(st))
-    if r < 0:
-        raise RuntimeError("oracle failed")
-    return dict(num_inliers=r, mask=mask.astype(bool), H=E.reshape(3, 3), stats=_stats_dict(st), rows=norm,
-                thr=thr_n.value)
+                                            mask.ctypes.data_as(_U8P), _dp(E), C.byref(st),
+                                            None if smp is None else C.byref(smp))
+    return _result(r, mask, E, st, smp, rows=norm, thr=thr_n.value)
 
 
 IMAGE_SIZE = (960.0, 1280.0, 960.0, 1280.0)          # h1, w1, h2, w2 of pygcransac.synthetic

@@ -3,8 +3,8 @@ function and every generator kernel against their host twins bit for bit,
 uniform sampling untouched, the C ABI's refusals, and whole runs: a local
 structure found within 64 iterations, runs that end by the uniform bound,
 determinism across batch_slots, the sharded entry, verify_batches and the graph
-cut beside the layers.  The oracle knows no NAPSAC: there is no whole-run
-oracle parity here."""
+cut beside the layers.  Whole-run parity with the oracle's restatement of
+NAPSAC is test_gpu_oracle_samplers.py's."""
 import ctypes as C
 
 import numpy as np

@@ -2,7 +2,8 @@
 function against the host sampler for all five correspondence solvers, the
 PROSAC generators against the host sampler + host minimal solvers, uniform
 sampling untouched, and whole runs on a budget uniform sampling cannot meet.
-The oracle knows no PROSAC: there is no whole-run oracle parity here."""
+Whole-run parity with the oracle's restatement of PROSAC is
+test_gpu_oracle_samplers.py's."""
 import ctypes as C
 
 import numpy as np

@@ -2,7 +2,9 @@
 stop kernel against its host twin on scenes and on crafted inlier patterns at
 the wave and tile boundaries; whole runs that end at the iteration floor and
 lose nothing; the same run on every replay path; the flag-clear run untouched;
-refusals.  The oracle knows no PROSAC: the header is the definition."""
+refusals.  The header is the definition; the oracle's restatement of it and of
+which model's (I*, n*) is in force at each update of the stop is compared with
+whole flagged runs in test_gpu_oracle_samplers.py."""
 import ctypes as C
 
 import numpy as np
