@@ -292,8 +292,16 @@ struct Workspace {
     DevBuf<GeoModel> gr_models;
     DevBuf<uint32_t> gr_hmap, gr_hcount, gr_n0, gr_n1;
     DevBuf<double> gr_v0, gr_v1, gr_tot;
+    // verify_batches' bound path (bound.h): one set per scoring stream, each
+    // array holding a launch group's batches back to back
+    struct BoundSet {
+        DevBuf<uint8_t> inc, state;
+        DevBuf<RectModel> models;
+        DevBuf<uint32_t> ub0, ub1, map, cnt, n0, n1;
+        DevBuf<double> v0, v1, tot;
+    } vbnd[3];
     hipEvent_t vb_flush = nullptr;
-    hipEvent_t vb_aux = nullptr;        // verify_batches: the aux scoring stream's last batch of a ring
+    hipEvent_t vb_aux = nullptr;       // verify_batches: the aux scoring stream's last batch of a ring
     DevBuf<uint32_t> rf_idx;            // GPU refit: inlier index lists
     PinBuf<uint32_t> rf_hidx;           // GPU refit: their pinned staging
     DevBuf<double> rf_A;                // GPU refit: A (3 columns) and b, column-major
@@ -1802,6 +1810,69 @@ struct RectTraits {
         const char* e = getenv("GCR_VERIFY_CHAIN");
         return !(e && e[0] == '0');
     }
+    // ---- the bound path (bound.h) ----
+    // Taken by verify_batches calls of at least 4 batches when the rounding
+    // guard holds, unless GCR_VERIFY_BOUND=0 or one of the fused path's A/B
+    // switches is set (read per call): a set switch pins the fused kernel, so
+    // the tests that compare those settings keep exercising the code they name.
+    static bool bound_on() {
+        const char* e = getenv("GCR_VERIFY_BOUND");
+        if (e && e[0] == '0') return false;
+        for (const char* sw : {"GCR_VERIFY_GROUPS", "GCR_VERIFY_GROUPS_STAGE", "GCR_VERIFY_CHAIN", "GCR_VERIFY_OVERLAP",
+                               "GCR_VERIFY_DEFER", "GCR_VERIFY_PIPE", "GCR_FM_PRECONST", "GCR_SCORER", "GCR_PROBE"})
+            if (getenv(sw) != nullptr) return false;
+        return true;
+    }
+    // The scale-only kinds stay on the fused path unless GCR_VERIFY_BOUND=1
+    // asks for the bound path: their one-class bound is too weak (M1 at the
+    // bench's shape scores 93 - 100 % of a batch's slots exactly and runs
+    // 268 us a batch against the fused path's 71, MEASUREMENTS.md §1).
+    static bool bound_path(gcr_problem* P, const double Tm[2], uint32_t nb) {
+        const int K = solver_classes(P->solver);
+        const uint64_t nf = (uint64_t)P->dp.cls[0].n + (K == 2 ? P->dp.cls[1].n : 0);
+        const char* e = getenv("GCR_VERIFY_BOUND");
+        const bool forced = e && e[0] == '1';
+        return nb >= 4 && bound_on() && (K == 2 || forced) && bnd::guard_holds(nf, Tm[0], Tm[1], K);
+    }
+    // GCR_VERIFY_BOUND_SEEDS (read per call): slots a batch scored before the
+    // contenders are chosen; default 64 (MEASUREMENTS.md §1)
+    static uint32_t bound_seeds() {
+        const char* e = getenv("GCR_VERIFY_BOUND_SEEDS");
+        const int v = e ? atoi(e) : 0;
+        return v >= 1 ? (uint32_t)std::min(v, 4096) : 64u;
+    }
+    static BoundLists bound_lists(gcr_problem* P, int set, uint32_t n, uint32_t gmax, uint32_t seeds, ScoreOut& sc) {
+        Workspace::BoundSet& b = P->w->vbnd[set];
+        BoundLists L;
+        L.seeds = seeds;
+        L.cap1 = bnd::seed_cap(seeds);
+        L.lstride = bnd::list_stride(n, L.cap1);
+        const size_t ns = (size_t)gmax * n, nl = (size_t)gmax * L.lstride;
+        b.inc.ensure(ns); b.state.ensure(ns); b.models.ensure(ns); b.ub0.ensure(ns); b.ub1.ensure(ns);
+        b.map.ensure(nl); b.cnt.ensure(2 * (size_t)gmax);
+        b.n0.ensure(nl); b.n1.ensure(nl); b.v0.ensure(nl); b.v1.ensure(nl); b.tot.ensure(nl);
+        L.ub0 = b.ub0.p; L.ub1 = b.ub1.p; L.state = b.state.p; L.map = b.map.p;
+        L.count1 = b.cnt.p; L.count2 = b.cnt.p + gmax;
+        sc = ScoreOut{b.n0.p, b.n1.p, b.v0.p, b.v1.p, b.tot.p};
+        return L;
+    }
+    // One launch group of `count` batches from slot s0 on stream s: generate,
+    // bound, seeds, their exact scores, contenders, theirs, selection -- all
+    // queued, the list sizes stay on the device.  rec[0 .. count): the records.
+    static hipError_t bound_group(gcr_problem* P, const double Tm[2], uint64_t seed, uint64_t s0, uint32_t n,
+                                  const uint32_t m[2], uint32_t count, int set, const BoundLists& L,
+                                  const ScoreOut& sc, BatchRecord* rec, hipStream_t s) {
+        Workspace::BoundSet& b = P->w->vbnd[set];
+        const uint32_t nh = count * n;
+        hipError_t e = launch_generate(P->dp, seed, s0, nh, b.inc.p, b.models.p, s);
+        if (e == hipSuccess) e = launch_bound(P->dp, Tm, b.models.p, b.inc.p, nh, L.ub0, L.ub1, s);
+        if (e == hipSuccess) e = launch_bound_seeds(P->solver, b.inc.p, b.models.p, n, count, m, L, s);
+        if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, 0, L, sc, s);
+        if (e == hipSuccess) e = launch_bound_contenders(P->solver, sc, n, count, m, Tm, L, s);
+        if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, 1, L, sc, s);
+        if (e == hipSuccess) e = launch_bound_select(P->solver, sc, b.inc.p, b.models.p, n, s0, count, m, Tm, L, rec, s);
+        return e;
+    }
     // LO fits on the host; the final hybrid refit solves big systems on the GPU
     static bool fit(gcr_problem* P, const std::vector<uint32_t>* lists, Model& out, bool final_refit) {
         if (!final_refit) return fit_nonminimal(P->solver, P->hc, lists, out);
@@ -2856,7 +2927,72 @@ public:
     // `nb` back-to-back batches of `nslots` slots starting at slot0, each
     // generated, scored and reduced to its first strict best on the device by
     // the fused scorer (launch_verify_fused); one host synchronisation at the end.
-    void verify_batches(uint64_t slot0, uint32_t nslots, uint32_t nb, gcr_batch_result* out) {
+    // gcr_debug_verify_bound: the bound path's per-slot bounds (nb * nslots
+    // each) and per batch the slots it scored exactly, copied out group by group
+    struct BoundCapture {
+        uint32_t* ub0;
+        uint32_t* ub1;
+        uint32_t* scored;
+        bool taken = false;                     // the call took the bound path
+    };
+    // The bound path (bound.h; Tr::bound_group): launch groups of up to G
+    // batches, clipped like the fused path's (fm_groups.h), go round s_, the
+    // aux stream and the side stream, each with its own buffer set.  A group
+    // is a chain of seven dependent launches, two of them the exact scorer
+    // with a few workgroups and ~170 us each, so one stream alone leaves the
+    // GPU idle most of the time: the other streams' bound kernels fill it.
+    // Every group ends with its own selection; evs[0..1] bracket the whole
+    // call on s_.
+    void verify_batches_bound(uint64_t slot0, uint32_t nslots, uint32_t nb, const uint32_t m32[2], BatchRecord* drecs,
+                              BoundCapture* cap) {
+        if constexpr (Tr::kFusedVerify) {
+            Workspace* w = P_->w;
+            constexpr int kStreams = 3;
+            hipStream_t streams[kStreams] = {s_, aux_stream(P_->ctx), P_->ctx->side};
+            for (hipEvent_t* e : {&w->vb_gen[0], &w->vb_gen[1], &w->vb_start})
+                if (*e == nullptr) HIPC(hipEventCreateWithFlags(e, hipEventDisableTiming));
+            const uint32_t R = Tr::select_ring(nslots);
+            uint32_t G = Tr::kVerifyGroups;
+            while (G > 1 && nb < 2 * G) G >>= 1;
+            while (G > 1 && R % G != 0) --G;
+            const uint32_t seeds = Tr::bound_seeds();
+            ScoreOut sc[kStreams];
+            BoundLists L[kStreams];
+            for (int set = 0; set < kStreams; ++set) L[set] = Tr::bound_lists(P_, set, nslots, G, seeds, sc[set]);
+            HIPC(hipEventRecord(w->evs[0], s_));
+            HIPC(hipEventRecord(w->vb_start, s_));
+            for (int k = 1; k < kStreams; ++k) HIPC(hipStreamWaitEvent(streams[k], w->vb_start, 0));
+            uint32_t li = 0;
+            for (uint32_t b = 0; b < nb; ++li) {
+                const uint32_t c = fmg::launch_batches(b, nb, G, R);
+                const int set = (int)(li % kStreams);
+                hipStream_t st = streams[set];
+                HIPC(Tr::bound_group(P_, Tm_, prm_.seed, slot0 + (uint64_t)b * nslots, nslots, m32, c, set, L[set],
+                                     sc[set], drecs + b, st));
+                if (cap != nullptr) {
+                    // debug hook: this group's bounds and list sizes (the copies
+                    // wait for the stream, so the set may be reused after them)
+                    const size_t o = (size_t)b * nslots, ns = (size_t)c * nslots;
+                    std::vector<uint32_t> cnt(2 * (size_t)G);
+                    HIPC(hipStreamSynchronize(st));
+                    HIPC(hipMemcpy(cap->ub0 + o, L[set].ub0, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                    HIPC(hipMemcpy(cap->ub1 + o, L[set].ub1, ns * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                    HIPC(hipMemcpy(cnt.data(), L[set].count1, cnt.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                    for (uint32_t k = 0; k < c; ++k) cap->scored[b + k] = cnt[k] + cnt[G + k];
+                    cap->taken = true;
+                }
+                b += c;
+            }
+            for (int k = 1; k < kStreams; ++k) {
+                HIPC(hipEventRecord(w->vb_gen[k - 1], streams[k]));
+                HIPC(hipStreamWaitEvent(s_, w->vb_gen[k - 1], 0));
+            }
+            HIPC(hipEventRecord(w->evs[1], s_));
+        }
+    }
+
+    void verify_batches(uint64_t slot0, uint32_t nslots, uint32_t nb, gcr_batch_result* out,
+                        BoundCapture* cap = nullptr) {
         static_assert(sizeof(BatchRecord) == sizeof(gcr_batch_result), "record layout");
         static_assert(offsetof(BatchRecord, best_model) == offsetof(gcr_batch_result, best_model), "record layout");
         const auto t0 = Clock::now();
@@ -2890,7 +3026,15 @@ public:
         }
         uint32_t timed = 0;
         uint32_t span_launches = 0;              // > 0: evs[0..1] bracket that many launches
-        if (Tr::kPipe && nb > 1 && pipe_on()) {
+        bool bound = false;
+        if constexpr (Tr::kFusedVerify) bound = Tr::bound_path(P_, Tm_, nb);
+        if (bound) {
+            if constexpr (Tr::kFusedVerify) {
+                verify_batches_bound(slot0, nslots, nb, m32, drecs, cap);
+                span_launches = nb;
+                timed = 1;
+            }
+        } else if (Tr::kPipe && nb > 1 && pipe_on()) {
             // two-stream pipeline (Tr::verify_gen / verify_score): generation
             // of batch b on the side stream once batch b - 2 (same buffer set)
             // has been scored; scoring of batch b on s_ once it is generated
@@ -5097,6 +5241,25 @@ int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint
             r.verify_batches(slot0, nslots, nbatches, out);
             fill_stats(stats_out, r.stats());
             return GCR_OK;
+        };
+        return with_runner(prob, *params, go);
+    });
+}
+
+int gcr_debug_verify_bound(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
+                           uint32_t nbatches, uint32_t* ub0_out, uint32_t* ub1_out, uint32_t* scored_out) {
+    if (!prob || !ub0_out || !ub1_out || !scored_out) return set_err(GCR_EINVAL, "null problem or output");
+    if (prob->solver > GCR_SOLVER_SIFT22) return set_err(GCR_EINVAL, "the bound path scores rectification solvers");
+    if (int e = check_params(params, prob->solver)) return e;
+    if (nslots == 0 || nbatches == 0) return set_err(GCR_EINVAL, "nslots and nbatches must be > 0");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        auto go = [&](auto&& r) {
+            typename std::decay_t<decltype(r)>::BoundCapture cap{ub0_out, ub1_out, scored_out};
+            std::vector<gcr_batch_result> recs(nbatches);
+            r.verify_batches(slot0, nslots, nbatches, recs.data(), &cap);
+            if (!cap.taken) return set_err(GCR_EINVAL, "this call does not take the bound path");
+            return (int)GCR_OK;
         };
         return with_runner(prob, *params, go);
     });

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <cstdint>
 
+#include "bound.h"
 #include "exact.h"
 #include "fund.h"
 #include "geo.h"
@@ -285,6 +286,40 @@ hipError_t launch_select_batches(const WgBest* wg, size_t wg_stride, const RectM
                                  uint32_t nslots, uint32_t count, BatchRecord* rec, hipStream_t stream);
 // true when launch_verify_fused at this batch size uses the chained kernel
 bool verify_chains(uint32_t nslots);
+
+// The bound path of gcr_problem_verify_batches (bound.h), for
+// `batches` consecutive batches of nslots slots whose inc / models / bounds /
+// states lie back to back (stride nslots) and whose lists lie lstride entries
+// apart: per batch one map and one set of score arrays, the seeds' entries at
+// [0, cap1), the contenders' from cap1 on (bnd::list_stride), count1 / count2
+// one word a batch.
+struct BoundLists {
+    uint32_t* ub0 = nullptr;        // per slot: scale features that pass the packed-fp32 pre-band
+    uint32_t* ub1 = nullptr;        // ... orientation features (0 for the scale-only kinds)
+    uint8_t* state = nullptr;       // per slot: bnd::kDead / kLive / kSeed
+    uint32_t* map = nullptr;
+    uint32_t* count1 = nullptr;
+    uint32_t* count2 = nullptr;
+    uint32_t seeds = 0, cap1 = 0, lstride = 0;
+};
+// k_bound<KIND>: ub0 / ub1 of nh slots (0 for a slot without a model)
+hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
+                        uint32_t nh, uint32_t* ub0, uint32_t* ub1, hipStream_t stream);
+// the seeds: about L.seeds live slots a batch with the largest ub0 + ub1, in slot order
+hipError_t launch_bound_seeds(int solver, const uint8_t* inc, const RectModel* models, uint32_t nslots,
+                              uint32_t batches, const uint32_t m[2], const BoundLists& L, hipStream_t stream);
+// exact scores (k_score_split<KIND, 4, 960>, the counts read on the device) of
+// every batch's seeds (list 0) or contenders (list 1) at their list positions
+hipError_t launch_score_lists(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
+                              uint32_t nslots, uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
+                              hipStream_t stream);
+// the contenders: live slots outside the seeds with ub0 + ub1 + 1 > the seeds' best finished score
+hipError_t launch_bound_contenders(int solver, const ScoreOut& sc, uint32_t nslots, uint32_t batches,
+                                   const uint32_t m[2], const double Tm[2], const BoundLists& L, hipStream_t stream);
+// rec[b]: batch b's record, the first strict best over both lists (slots from slot0 + b nslots)
+hipError_t launch_bound_select(int solver, const ScoreOut& sc, const uint8_t* inc, const RectModel* models,
+                               uint32_t nslots, uint64_t slot0, uint32_t batches, const uint32_t m[2],
+                               const double Tm[2], const BoundLists& L, BatchRecord* rec, hipStream_t stream);
 
 // The correspondence estimators' counterparts of launch_generate /
 // launch_score / launch_mask / launch_select.  `solver` is the estimator

@@ -834,6 +834,21 @@ __global__ __launch_bounds__(kSplitThreads) void k_score_split(DevProblem p, dou
     if constexpr (KIND >= 3) {
         if (gen.hcount != nullptr) nh = min(nh_in, *gen.hcount);
         if (blockIdx.x * H >= nh) return;            // whole workgroup, before any barrier
+    } else if constexpr (!kGen) {
+        // lists of the bound path (launch_score_lists): list blockIdx.y's map,
+        // count and outputs lie gen.slot_stride entries (one count) after list
+        // blockIdx.y - 1's, its models and inc gen.models_stride entries;
+        // hypothesis j of a list is model hmap[j], j < its count
+        if (gen.hcount != nullptr) {
+            const size_t o = (size_t)blockIdx.y * gen.slot_stride;
+            models += (size_t)blockIdx.y * gen.models_stride;
+            if (inc != nullptr) inc += (size_t)blockIdx.y * gen.models_stride;
+            gen.hmap += o;
+            out.n0 += o; out.n1 += o; out.v0 += o; out.v1 += o; out.tot += o;
+            if (out.fl) out.fl += o;
+            nh = min(nh_in, gen.hcount[blockIdx.y]);
+            if (blockIdx.x * H >= nh) return;        // whole workgroup, before any barrier
+        }
     }
     static_assert(H * R <= 65536, "queue entries are 16-bit tile indices");
     constexpr int kPer = H * R / kComputeThreads;    // pairs per compute thread per round
@@ -871,7 +886,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_score_split(DevProblem p, dou
     const int fsub = t / H;
     const uint32_t hg = blockIdx.x * H + h;
     // model / inc index of this hypothesis (compacted launches: the map)
-    const uint32_t mi = (KIND >= 3 && gen.hmap != nullptr && hg < nh) ? gen.hmap[hg] : hg;
+    const uint32_t mi = ((KIND >= 3 || !kGen) && gen.hmap != nullptr && hg < nh) ? gen.hmap[hg] : hg;
 
     const uint32_t n0 = p.cls[0].n;
     const uint32_t n1 = (KIND == 2) ? p.cls[1].n : 0;
@@ -966,7 +981,7 @@ __global__ __launch_bounds__(kSplitThreads) void k_score_split(DevProblem p, dou
         const bool v = valid_h;
         RectModel m = default_model();
         if constexpr (KIND < 3) {
-            m = v ? (kGen ? gen_m[h] : models[hg]) : default_model();
+            m = v ? (kGen ? gen_m[h] : models[mi]) : default_model();
             hyp[h] = make_hyp<KIND>(m, band0);
         }
     }
@@ -4728,6 +4743,340 @@ __global__ __launch_bounds__(kSelectThreads) void k_select_wg(const WgBest* __re
     }
 }
 
+// ----------------------------------------------------------- bound path ----
+// gcr_problem_verify_batches' second path: a slot's finished
+// score is at most its inlier count, and that at most the number of features
+// the packed-fp32 pre-band lets through (the exact pass only ever sees those).
+// k_bound counts them per slot, k_bound_seeds picks the slots with the
+// largest bounds, an exact scorer scores them, k_bound_contenders lists every
+// other slot whose bound could still reach the seeds' best, the scorer scores
+// those, and k_bound_select takes the first strict best over both lists.
+//
+// k_bound: a wave owns kBoundHW consecutive slots and walks every feature, one
+// feature a lane and round, with exactly the scorer's constants (make_hyp,
+// rpb_setup) and tests (rpb_scale, rpb_orient).  The reject masks are compare
+// ballots, so the counts are scalar bit counts; nothing is queued or stored
+// until the two counts of each slot at the end.  LDS holds the wave's
+// constant records only.
+constexpr int kBoundThreads = 256;
+constexpr int kBoundWaves = kBoundThreads / 64;
+constexpr int kBoundHW = 16;
+
+template <int KIND>
+__global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double band0, double tan_tau1,
+                                                         const RectModel* __restrict__ models,
+                                                         const uint8_t* __restrict__ inc, uint32_t nh,
+                                                         uint32_t* __restrict__ ub0, uint32_t* __restrict__ ub1) {
+    static_assert(KIND <= 2 && kBoundHW % 2 == 0 && kBoundHW <= 64, "rectification kinds, whole pairs");
+    __shared__ RPairBand pbs[kBoundWaves][kBoundHW / 2];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const uint32_t h0 = (blockIdx.x * kBoundWaves + (uint32_t)wave) * kBoundHW;
+    bool v = false;
+    if (lane < kBoundHW) {
+        const uint32_t hg = h0 + lane;
+        v = hg < nh && inc[hg] <= 101;
+        const RectModel m = v ? models[hg] : default_model();
+        const HypConst q = make_hyp<KIND>(m, band0);
+        rpb_setup(pbs[wave], lane, q, p.cls[0].amax, p.cls[1].amax, tan_tau1, KIND == 2, v);
+    }
+    __syncthreads();
+    if (h0 >= nh) return;
+    const RPairBand* pb = pbs[wave];
+    uint32_t cnt0[kBoundHW], cnt1[kBoundHW];
+#pragma unroll
+    for (int q = 0; q < kBoundHW; ++q) cnt0[q] = cnt1[q] = 0;
+    {
+        const DevClass& c = p.cls[0];
+        const uint32_t n = c.n;
+        // the next round's features are loaded before this round's tests
+        double nx[3] = {0.0, 0.0, 0.0};
+        auto load = [&](uint32_t base) {
+            const uint32_t i = base + lane;
+            const uint32_t ii = i < n ? i : 0u;      // out-of-range lanes read feature 0 and are masked
+            nx[0] = c.x[ii]; nx[1] = c.y[ii]; nx[2] = c.a[ii];
+        };
+        if (n > 0) load(0);
+        for (uint32_t base = 0; base < n; base += 64) {
+            const bool ok = base + lane < n;
+            const double f0 = nx[0], f1 = nx[1], f2 = nx[2];
+            if (base + 64 < n) load(base + 64);
+            const uint64_t okm = __builtin_amdgcn_ballot_w64(ok);
+            const float pa = (float)f0, pb1 = (float)f1;
+            const float pc = (f2 >= 0x1p-100 && f2 <= 0x1p100) ? (float)f2 : __builtin_nanf("");
+            static_for<0, kBoundHW / 2>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                uint64_t r0, r1;
+                rpb_scale(rpb_scale_c(pb[j]), pa, pb1, pc, r0, r1);
+                cnt0[2 * j] += (uint32_t)__builtin_popcountll(okm & ~r0);
+                cnt0[2 * j + 1] += (uint32_t)__builtin_popcountll(okm & ~r1);
+            });
+        }
+    }
+    if constexpr (KIND == 2) {
+        const DevClass& c = p.cls[1];
+        const uint32_t n = c.n;
+        double nx[4] = {0.0, 0.0, 0.0, 0.0};
+        auto load = [&](uint32_t base) {
+            const uint32_t i = base + lane;
+            const uint32_t ii = i < n ? i : 0u;
+            nx[0] = c.x[ii]; nx[1] = c.y[ii]; nx[2] = c.c0[ii]; nx[3] = c.c1[ii];
+        };
+        if (n > 0) load(0);
+        for (uint32_t base = 0; base < n; base += 64) {
+            const bool ok = base + lane < n;
+            const double f0 = nx[0], f1 = nx[1], f2 = nx[2], f3 = nx[3];
+            if (base + 64 < n) load(base + 64);
+            const uint64_t okm = __builtin_amdgcn_ballot_w64(ok);
+            const float xf = (float)f0, yf = (float)f1;
+            const float pb1 = (float)f2;                        // cos theta
+            const float pc = (float)f3;                         // sin theta
+            const float pa = __builtin_fmaf(xf, pc, -(yf * pb1));   // g = x st - y ct
+            static_for<0, kBoundHW / 2>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                uint64_t r0, r1;
+                rpb_orient(rpb_orient_c(pb[j]), pa, pb1, pc, r0, r1);
+                cnt1[2 * j] += (uint32_t)__builtin_popcountll(okm & ~r0);
+                cnt1[2 * j + 1] += (uint32_t)__builtin_popcountll(okm & ~r1);
+            });
+        }
+    }
+    uint32_t my0 = 0, my1 = 0;
+    static_for<0, kBoundHW>([&](auto qc) {
+        constexpr int q = decltype(qc)::value;
+        my0 = lane == q ? cnt0[q] : my0;
+        my1 = lane == q ? cnt1[q] : my1;
+    });
+    if (lane < kBoundHW && h0 + lane < nh) {
+        ub0[h0 + lane] = v ? my0 : 0u;
+        ub1[h0 + lane] = v ? my1 : 0u;
+    }
+}
+
+// Order-preserving list of the entries j < n with keep(j), cut at `cap`
+// entries: every thread of the 1024-thread workgroup calls it; returns the
+// number kept before the cut.  wsum: kSelectThreads / 64 words of LDS.
+template <class F>
+__device__ __forceinline__ uint32_t bound_list(uint32_t n, uint32_t cap, uint32_t* __restrict__ map, uint32_t* wsum,
+                                               F&& keep) {
+    constexpr uint32_t kWaves = kSelectThreads / 64;
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    uint32_t base = 0;
+    for (uint32_t t0 = 0; t0 < n; t0 += kSelectThreads) {
+        const uint32_t j = t0 + t;
+        const bool k = j < n && keep(j);
+        const uint64_t m = __builtin_amdgcn_ballot_w64(k);
+        const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+        if (lane == 0) wsum[w] = (uint32_t)__builtin_popcountll(m);
+        __syncthreads();
+        uint32_t wb = 0, tot = 0;
+#pragma unroll
+        for (uint32_t x = 0; x < kWaves; ++x) {
+            const uint32_t sv = wsum[x];
+            wb += x < w ? sv : 0u;
+            tot += sv;
+        }
+        const uint32_t o = base + wb + below;
+        if (k && o < cap) map[o] = j;
+        base += tot;
+        __syncthreads();                                 // wsum is rewritten by the next tile
+    }
+    return base;
+}
+
+// Seeds of batch blockIdx.x: a slot is live when it has a model, its bounds
+// reach the minimal counts (else its finish is zero), their sum is positive
+// and (2-SIFT) the model is valid.  The seeds are the live slots whose bound
+// ub0 + ub1 lies in the top bins of a 1024-bin histogram over [0, max] -- the
+// fewest bins from the top that hold `seeds` slots -- in slot order, at most
+// cap1 of them.  Which slots are seeds changes the work, never the record.
+// state[j]: bnd::kDead / kLive / kSeed for the contender kernel.
+__global__ __launch_bounds__(kSelectThreads) void k_bound_seeds(int solver, const uint8_t* __restrict__ inc,
+                                                                const RectModel* __restrict__ models,
+                                                                const uint32_t* __restrict__ ub0,
+                                                                const uint32_t* __restrict__ ub1, uint32_t n,
+                                                                uint32_t m0, uint32_t m1, uint32_t seeds,
+                                                                uint32_t cap1, uint32_t lstride,
+                                                                uint32_t* __restrict__ map,
+                                                                uint32_t* __restrict__ count1,
+                                                                uint8_t* __restrict__ state) {
+    const size_t o = (size_t)blockIdx.x * n;
+    inc += o; models += o; ub0 += o; ub1 += o; state += o;
+    map += (size_t)blockIdx.x * lstride;
+    __shared__ uint32_t hist[1024];
+    __shared__ uint32_t wsum[kSelectThreads / 64];
+    __shared__ uint32_t s_max, s_cut;
+    const uint32_t t = threadIdx.x;
+    const int K = solver_classes(solver);
+    // key: the bound of a live slot (>= 1), 0 otherwise
+    auto key = [&](uint32_t j) -> uint32_t {
+        if (inc[j] > 101) return 0u;
+        const uint32_t a = ub0[j], b = K == 2 ? ub1[j] : 0u;
+        if (a < m0 || (K == 2 && b < m1)) return 0u;
+        if (solver == GCR_SOLVER_SIFT22 && !valid_model_sift22(models[j])) return 0u;
+        return a + b;
+    };
+    hist[t] = 0;
+    if (t == 0) s_max = 0;
+    __syncthreads();
+    uint32_t mx = 0;
+    for (uint32_t j = t; j < n; j += kSelectThreads) mx = max(mx, key(j));
+    if (mx) atomicMax(&s_max, mx);
+    __syncthreads();
+    const uint64_t span = (uint64_t)s_max + 1u;
+    auto bin = [&](uint32_t k) -> uint32_t { return (uint32_t)(((uint64_t)k << 10) / span); };
+    for (uint32_t j = t; j < n; j += kSelectThreads) {
+        const uint32_t k = key(j);
+        if (k) atomicAdd(&hist[bin(k)], 1u);
+    }
+    __syncthreads();
+    if (t == 0) {
+        uint32_t c = 0, b = 1024;
+        while (b > 0 && c < seeds) c += hist[--b];
+        s_cut = b;
+    }
+    __syncthreads();
+    const uint32_t cut = s_cut;
+    const uint32_t kept = bound_list(n, cap1, map, wsum, [&](uint32_t j) {
+        const uint32_t k = key(j);
+        return k != 0 && bin(k) >= cut;
+    });
+    const uint32_t c1 = min(kept, cap1);
+    if (t == 0) count1[blockIdx.x] = c1;
+    __syncthreads();
+    // the slots' states: the first c1 kept slots are the seeds (map is in slot
+    // order, so a kept slot is a seed iff it is at most the last listed one)
+    const uint32_t last = c1 ? map[c1 - 1] : 0u;
+    for (uint32_t j = t; j < n; j += kSelectThreads) {
+        const uint32_t k = key(j);
+        state[j] = k == 0 ? bnd::kDead : (c1 && j <= last && bin(k) >= cut) ? bnd::kSeed : bnd::kLive;
+    }
+}
+
+// Contenders of batch blockIdx.x: S = the largest finished score over the
+// seeds that are candidates of the update rule (score > 0; the seeds' models
+// are valid), 0 without one; every live slot outside the seed list with
+// ub0 + ub1 + 1 > S goes, in slot order, into the second list at map[cap1 ..].
+// With the rounding guard (bound.h) a slot left out scores strictly below S.
+__global__ __launch_bounds__(kSelectThreads) void k_bound_contenders(int solver, ScoreOut sc,
+                                                                     const uint32_t* __restrict__ ub0,
+                                                                     const uint32_t* __restrict__ ub1,
+                                                                     const uint8_t* __restrict__ state, uint32_t n,
+                                                                     uint32_t m0, uint32_t m1, double Tm0, double Tm1,
+                                                                     uint32_t cap1, uint32_t lstride,
+                                                                     uint32_t* __restrict__ map,
+                                                                     const uint32_t* __restrict__ count1,
+                                                                     uint32_t* __restrict__ count2) {
+    const size_t o = (size_t)blockIdx.x * n, lo = (size_t)blockIdx.x * lstride;
+    ub0 += o; ub1 += o; state += o;
+    map += lo;
+    sc.n0 += lo; sc.n1 += lo; sc.v0 += lo; sc.v1 += lo; sc.tot += lo;
+    __shared__ double s_val[kSelectThreads / 64];
+    __shared__ uint32_t wsum[kSelectThreads / 64];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int K = solver_classes(solver);
+    const uint32_t c1 = min(count1[blockIdx.x], cap1);
+    double best = 0.0;
+    for (uint32_t j = t; j < c1; j += kSelectThreads) {
+        const double s = bnd::finish(sc.tot[j], sc.v0[j], sc.v1[j], sc.n0[j], sc.n1[j], m0, m1, Tm0, Tm1, K);
+        if (best < s) best = s;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        const double x = __shfl_xor(best, d);
+        if (best < x) best = x;
+    }
+    if (lane == 0) s_val[w] = best;
+    __syncthreads();
+    double S = 0.0;
+#pragma unroll
+    for (uint32_t x = 0; x < kSelectThreads / 64; ++x)
+        if (S < s_val[x]) S = s_val[x];
+    __syncthreads();
+    const uint32_t kept = bound_list(n, n, map + cap1, wsum, [&](uint32_t j) {
+        if (state[j] != bnd::kLive) return false;
+        const uint32_t b = ub0[j] + (K == 2 ? ub1[j] : 0u);
+        return (double)b + 1.0 > S;
+    });
+    if (t == 0) count2[blockIdx.x] = kept;
+}
+
+// The record of batch blockIdx.x: first strict best over both lists -- the
+// largest finished score > 0 with the lowest slot (the lists hold live slots
+// only: models present and valid) -- and the batch's models / iterations
+// summed over every slot's inc, as k_select does.
+__global__ __launch_bounds__(kSelectThreads) void k_bound_select(int solver, ScoreOut sc,
+                                                                 const uint8_t* __restrict__ inc,
+                                                                 const RectModel* __restrict__ models, uint32_t n,
+                                                                 uint64_t slot0, uint32_t m0, uint32_t m1, double Tm0,
+                                                                 double Tm1, uint32_t cap1, uint32_t lstride,
+                                                                 const uint32_t* __restrict__ map,
+                                                                 const uint32_t* __restrict__ count1,
+                                                                 const uint32_t* __restrict__ count2,
+                                                                 BatchRecord* out) {
+    const size_t o = (size_t)blockIdx.x * n, lo = (size_t)blockIdx.x * lstride;
+    inc += o; models += o;
+    map += lo;
+    sc.n0 += lo; sc.n1 += lo; sc.v0 += lo; sc.v1 += lo; sc.tot += lo;
+    slot0 += (uint64_t)blockIdx.x * n;
+    out += blockIdx.x;
+    __shared__ double s_val[kSelectThreads];
+    __shared__ uint32_t s_slot[kSelectThreads], s_pos[kSelectThreads];
+    __shared__ unsigned long long s_models[kSelectThreads], s_its[kSelectThreads];
+    const int t = threadIdx.x;
+    const int K = solver_classes(solver);
+    double best = 0.0;
+    uint32_t bs = 0xffffffffu, bp = 0;
+    unsigned long long nm = 0, its = 0;
+    for (uint32_t j = t; j < n; j += kSelectThreads) {
+        const uint32_t in = inc[j];
+        its += in <= 102 ? in : 0;
+        nm += in <= 101 ? 1 : 0;
+    }
+    const uint32_t c1 = min(count1[blockIdx.x], cap1), c2 = min(count2[blockIdx.x], n);
+    for (uint32_t j = t; j < c1 + c2; j += kSelectThreads) {
+        const uint32_t pos = j < c1 ? j : cap1 + (j - c1);
+        const uint32_t slot = map[pos];
+        const double s = bnd::finish(sc.tot[pos], sc.v0[pos], sc.v1[pos], sc.n0[pos], sc.n1[pos], m0, m1, Tm0, Tm1, K);
+        if (s > 0.0 && (best < s || (best == s && slot < bs))) {
+            best = s;
+            bs = slot;
+            bp = pos;
+        }
+    }
+    s_val[t] = best; s_slot[t] = bs; s_pos[t] = bp; s_models[t] = nm; s_its[t] = its;
+    __syncthreads();
+    for (int w = kSelectThreads / 2; w > 0; w >>= 1) {
+        if (t < w) {
+            const uint32_t ia = s_slot[t], ib = s_slot[t + w];
+            const double va = s_val[t], vb = s_val[t + w];
+            if (ib != 0xffffffffu && (ia == 0xffffffffu || vb > va || (vb == va && ib < ia))) {
+                s_slot[t] = ib; s_val[t] = vb; s_pos[t] = s_pos[t + w];
+            }
+            s_models[t] += s_models[t + w];
+            s_its[t] += s_its[t + w];
+        }
+        __syncthreads();
+    }
+    if (t == 0) {
+        BatchRecord r;
+        r.models = s_models[0];
+        r.iterations = s_its[0];
+        r.best_slot = -1;
+        r.best_score = 0.0;
+        r.best_inliers[0] = r.best_inliers[1] = 0;
+        r.best_model = default_model();
+        if (s_slot[0] != 0xffffffffu) {
+            r.best_slot = (int64_t)(slot0 + s_slot[0]);
+            r.best_score = s_val[0];
+            r.best_inliers[0] = sc.n0[s_pos[0]];
+            r.best_inliers[1] = K == 2 ? sc.n1[s_pos[0]] : 0;
+            r.best_model = models[s_slot[0]];
+        }
+        *out = r;
+    }
+}
+
 // ----------------------------------------------------------------- mask ----
 template <int KIND>
 __global__ __launch_bounds__(kMaskBlock) void k_mask(DevClass c, int cls, typename ModelOf<KIND>::type m, int rule,
@@ -5156,6 +5505,72 @@ hipError_t launch_select_batches(const WgBest* wg, size_t wg_stride, const RectM
     const uint32_t nwg = (nslots + split_h(nslots) - 1) / split_h(nslots);
     hipLaunchKernelGGL(k_select_wg, dim3(count), dim3(kSelectThreads), 0, stream, wg, nwg, models, slot0, rec,
                        (uint32_t)wg_stride, nslots);
+    return hipGetLastError();
+}
+
+// ---- the bound path's launches (kernels.h) ----
+hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
+                        uint32_t nh, uint32_t* ub0, uint32_t* ub1, hipStream_t stream) {
+    if (nh == 0) return hipSuccess;
+    if (p.kind > GCR_SOLVER_SIFT22) return hipErrorInvalidValue;
+    double band0, tan_tau1;
+    band_consts(T, band0, tan_tau1);
+    const dim3 grid((nh + kBoundWaves * kBoundHW - 1) / (kBoundWaves * kBoundHW)), block(kBoundThreads);
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL(k_bound<0>, grid, block, 0, stream, p, band0, tan_tau1, models, inc, nh, ub0, ub1); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL(k_bound<1>, grid, block, 0, stream, p, band0, tan_tau1, models, inc, nh, ub0, ub1); break;
+        default: hipLaunchKernelGGL(k_bound<2>, grid, block, 0, stream, p, band0, tan_tau1, models, inc, nh, ub0, ub1); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_bound_seeds(int solver, const uint8_t* inc, const RectModel* models, uint32_t nslots,
+                              uint32_t batches, const uint32_t m[2], const BoundLists& L, hipStream_t stream) {
+    if (batches == 0 || nslots == 0) return hipSuccess;
+    if (L.lstride < bnd::list_stride(nslots, L.cap1) || L.seeds == 0) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bound_seeds, dim3(batches), dim3(kSelectThreads), 0, stream, solver, inc, models, L.ub0, L.ub1,
+                       nslots, m[0], m[1], L.seeds, L.cap1, L.lstride, L.map, L.count1, L.state);
+    return hipGetLastError();
+}
+
+hipError_t launch_score_lists(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
+                              uint32_t nslots, uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
+                              hipStream_t stream) {
+    if (batches == 0 || nslots == 0) return hipSuccess;
+    if (p.kind > GCR_SOLVER_SIFT22) return hipErrorInvalidValue;
+    constexpr int H = 4, R = 960;
+    const uint32_t off = list ? L.cap1 : 0u, cap = list ? nslots : L.cap1;
+    ScoreOut o{out.n0 + off, out.n1 + off, out.v0 + off, out.v1 + off, out.tot + off};
+    GenArgs g{};
+    g.hmap = L.map + off;
+    g.hcount = list ? L.count2 : L.count1;
+    g.slot_stride = L.lstride;
+    g.models_stride = nslots;
+    const dim3 grid((cap + H - 1) / H, batches), block(kSplitThreads);
+    double band0, tan_tau1;
+    band_consts(T, band0, tan_tau1);
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_score_split<0, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, cap, o, g); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_score_split<1, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, cap, o, g); break;
+        default: hipLaunchKernelGGL((k_score_split<2, H, R, false>), grid, block, 0, stream, p, T[0], T[1], band0, tan_tau1, flag_band(T), models, inc, cap, o, g); break;
+    }
+    return hipGetLastError();
+}
+
+hipError_t launch_bound_contenders(int solver, const ScoreOut& sc, uint32_t nslots, uint32_t batches,
+                                   const uint32_t m[2], const double Tm[2], const BoundLists& L, hipStream_t stream) {
+    if (batches == 0 || nslots == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bound_contenders, dim3(batches), dim3(kSelectThreads), 0, stream, solver, sc, L.ub0, L.ub1,
+                       L.state, nslots, m[0], m[1], Tm[0], Tm[1], L.cap1, L.lstride, L.map, L.count1, L.count2);
+    return hipGetLastError();
+}
+
+hipError_t launch_bound_select(int solver, const ScoreOut& sc, const uint8_t* inc, const RectModel* models,
+                               uint32_t nslots, uint64_t slot0, uint32_t batches, const uint32_t m[2],
+                               const double Tm[2], const BoundLists& L, BatchRecord* rec, hipStream_t stream) {
+    if (batches == 0 || nslots == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_bound_select, dim3(batches), dim3(kSelectThreads), 0, stream, solver, sc, inc, models, nslots,
+                       slot0, m[0], m[1], Tm[0], Tm[1], L.cap1, L.lstride, L.map, L.count1, L.count2, rec);
     return hipGetLastError();
 }
 

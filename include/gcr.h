@@ -469,6 +469,16 @@ int gcr_debug_score(gcr_problem* prob, const gcr_params* params, const gcr_rect_
  * sampler seed is params->seed */
 int gcr_debug_verify_slots(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
                            uint8_t* inc_out, uint32_t* n0, uint32_t* n1, double* v0, double* v1, double* tot);
+/* The bound path of gcr_problem_verify_batches (rectification solvers, calls
+ * of at least 4 batches; GCR_VERIFY_BOUND=0 or a set A/B switch of the fused
+ * path disables it): the same launches as that call's, returning per slot the
+ * features that pass the conservative pre-band -- ub0_out / ub1_out,
+ * nbatches * nslots entries each, upper bounds of the slot's inlier counts, 0
+ * for a slot without a model -- and per batch in scored_out[nbatches] how many
+ * slots were scored exactly.  GCR_EINVAL when the call would not take the
+ * bound path. */
+int gcr_debug_verify_bound(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
+                           uint32_t nbatches, uint32_t* ub0_out, uint32_t* ub1_out, uint32_t* scored_out);
 /* The run loop's score comparison `score(a) < score(b)` (GCRANSAC.h:440) as
  * gcr_problem_run takes it: both models scored by the GPU small scorer (value
  * scores), compared directly when they are further apart than their proven
