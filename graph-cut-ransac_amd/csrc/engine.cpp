@@ -63,6 +63,8 @@
 #include "host_pool.h"
 #include "match.h"
 #include "match_geo.h"
+#include "match_select.h"
+#include "match_sets.h"
 
 using namespace gcr;
 
@@ -548,6 +550,7 @@ struct gcr_ctx {
     // cost milliseconds)
     std::mutex ws_mu;
     std::vector<std::unique_ptr<Workspace>> ws_free;
+    MatchWorkspace match_ws;            // the descriptor sets' matching workspace (match_sets.h)
 };
 
 // A communicator rank for the hypothesis-sharded run (RCCL, one process per
@@ -5053,6 +5056,7 @@ void gcr_destroy(gcr_ctx* ctx) {
     if (ctx->pev0) (void)hipEventDestroy(ctx->pev0);
     if (ctx->pev1) (void)hipEventDestroy(ctx->pev1);
     if (ctx->pdone) (void)hipEventDestroy(ctx->pdone);
+    match_workspace_free(ctx->match_ws);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -6569,6 +6573,197 @@ void gcr_match_tiling(uint32_t out[3]) {
     out[0] = kMatchRowsPerWg;
     out[1] = kMatchStepCols;
     out[2] = kMatchSplitMinCols;
+}
+
+// ------------------------------------------------- resident descriptor sets --
+int gcr_descriptors_create(gcr_ctx* ctx, const uint8_t* d, size_t n, uint32_t dim, const double* positions,
+                           gcr_descriptors** out) {
+    if (!out) return set_err(GCR_EINVAL, "descriptors_create: out is NULL");
+    if (!d) return set_err(GCR_EINVAL, "descriptors_create: d is NULL");
+    if (n == 0 || n > kMatchMaxRows) return set_err(GCR_EINVAL, "descriptors_create: n must be in 1 .. 2^24");
+    if (dim < kMatchDimStep || dim > kMatchDimMax || dim % kMatchDimStep != 0)
+        return set_err(GCR_EINVAL, "descriptors_create: dim must be a multiple of 32 in 32 .. 512");
+    if (positions)
+        for (size_t k = 0; k < 2 * n; ++k)
+            if (!(__builtin_fabs(positions[k]) <= DBL_MAX))
+                return set_err(GCR_EINVAL, "descriptors_create: positions has a non-finite entry");
+    if (!ctx) return set_err(GCR_EINVAL, "descriptors_create: null context");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        auto s = std::unique_ptr<gcr_descriptors>(new gcr_descriptors());
+        s->ctx = ctx;
+        HIPC(match_set_create(ctx->stream, d, n, dim, positions, s.get()));
+        *out = s.release();
+        return GCR_OK;
+    });
+}
+
+void gcr_descriptors_destroy(gcr_descriptors* set) {
+    if (!set) return;
+    (void)hipSetDevice(set->ctx->device);
+    // a call of another thread may still read the set
+    (void)hipStreamSynchronize(set->ctx->stream);
+    match_set_destroy(set);
+    delete set;
+}
+
+int gcr_descriptors_info(const gcr_descriptors* set, size_t* n_out, uint32_t* dim_out, int* has_positions_out) {
+    if (!set) return set_err(GCR_EINVAL, "descriptors_info: set is NULL");
+    if (n_out) *n_out = set->n;
+    if (dim_out) *dim_out = set->dim;
+    if (has_positions_out) *has_positions_out = set->pos != nullptr;
+    return GCR_OK;
+}
+
+namespace {
+// nullptr, or the message naming the first bad option
+const char* match_options_check(const gcr_match_options* opt, bool guided, MatchSelectRule* rule) {
+    if (!opt) return "opt is NULL";
+    if (opt->has_ratio != 0 && opt->has_ratio != 1) return "opt.has_ratio must be 0 or 1";
+    if (opt->has_ratio && !(opt->rr > 0.0 && opt->rr <= DBL_MAX)) return "opt.rr must be finite and > 0";
+    if (opt->mutual != 0 && opt->mutual != 1) return "opt.mutual must be 0 or 1";
+    if (opt->has_max_distance != 0 && opt->has_max_distance != 1) return "opt.has_max_distance must be 0 or 1";
+    if (opt->has_max_distance && !guided) return "opt.has_max_distance is for the guided entries only";
+    if (opt->has_max_distance && !(opt->max_distance >= 0.0)) return "opt.max_distance must be >= 0, not NaN";
+    rule->guided = guided ? 1 : 0;
+    rule->has_ratio = opt->has_ratio;
+    rule->rr = opt->has_ratio ? opt->rr : 0.0;
+    rule->has_max_distance = opt->has_max_distance;
+    rule->max_distance = opt->has_max_distance ? opt->max_distance : 0.0;
+    return nullptr;
+}
+
+const char* match_set_pair_check(const gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b) {
+    if (!a) return "a is NULL";
+    if (!b) return "b is NULL";
+    if (a->ctx != ctx) return "a was created on another context";
+    if (b->ctx != ctx) return "b was created on another context";
+    if (a->dim != b->dim) return "a and b differ in dim";
+    return nullptr;
+}
+
+int match_sets_entry(const char* who, gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, bool guided,
+                     int kind, const double* model, double sq_threshold, const gcr_match_options* opt,
+                     uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out, double* ms_kernel_out) {
+    // the NULL checks first: they need no context, so they are reachable without a GPU
+    if (!a) return set_err(GCR_EINVAL, "%s: a is NULL", who);
+    if (!b) return set_err(GCR_EINVAL, "%s: b is NULL", who);
+    if (!opt) return set_err(GCR_EINVAL, "%s: opt is NULL", who);
+    if (!ctx) return set_err(GCR_EINVAL, "%s: null context", who);
+    if (const char* bad = match_set_pair_check(ctx, a, b)) return set_err(GCR_EINVAL, "%s: %s", who, bad);
+    MatchSetsPair p{};
+    if (const char* bad = match_options_check(opt, guided, &p.rule)) return set_err(GCR_EINVAL, "%s: %s", who, bad);
+    if (!matches_out) return set_err(GCR_EINVAL, "%s: matches_out is NULL", who);
+    if (!ratios_out) return set_err(GCR_EINVAL, "%s: ratios_out is NULL", who);
+    if (!m_out) return set_err(GCR_EINVAL, "%s: m_out is NULL", who);
+    if (guided) {
+        if (!a->pos) return set_err(GCR_EINVAL, "%s: a has no positions", who);
+        if (!b->pos) return set_err(GCR_EINVAL, "%s: b has no positions", who);
+        // kind, model and sq_threshold as gcr_match_descriptors_guided checks them
+        if (const char* bad = match_geo_check_model(kind, model, sq_threshold)) return set_err(GCR_EINVAL, "%s", bad);
+        p.kind = kind;
+        for (int k = 0; k < 9; ++k) p.model[k] = model[k];
+        p.T = sq_threshold;
+    }
+    if (cap < a->n) return set_err(GCR_EINVAL, "%s: cap must be at least a's row count (%zu), got %zu", who, a->n, cap);
+    p.a = a;
+    p.b = b;
+    p.mutual = opt->mutual;
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        const size_t offsets[2] = {0, a->n};
+        HIPC(match_sets_run(ctx->stream, ctx->n_cu, ctx->match_ws, &p, 1, offsets, matches_out, ratios_out, m_out,
+                            ms_kernel_out));
+        return GCR_OK;
+    });
+}
+}  // namespace
+
+int gcr_match_sets(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, const gcr_match_options* opt,
+                   uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out, double* ms_kernel_out) {
+    return match_sets_entry("match_sets", ctx, a, b, false, 0, nullptr, 0.0, opt, matches_out, ratios_out, cap, m_out,
+                            ms_kernel_out);
+}
+
+int gcr_match_sets_guided(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, int kind,
+                          const double* model, double sq_threshold, const gcr_match_options* opt,
+                          uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out,
+                          double* ms_kernel_out) {
+    return match_sets_entry("match_sets_guided", ctx, a, b, true, kind, model, sq_threshold, opt, matches_out,
+                            ratios_out, cap, m_out, ms_kernel_out);
+}
+
+int gcr_match_set_pairs(gcr_ctx* ctx, const gcr_descriptors* const* sets, size_t nsets, const uint32_t* pairs,
+                        size_t npairs, const gcr_match_options* opt, uint32_t* matches_out, double* ratios_out,
+                        const size_t* offsets, size_t* m_out, double* ms_kernel_out) {
+    const char* who = "match_set_pairs";
+    if (!sets) return set_err(GCR_EINVAL, "%s: sets is NULL", who);
+    MatchSelectRule rule{};
+    if (const char* bad = match_options_check(opt, false, &rule)) return set_err(GCR_EINVAL, "%s: %s", who, bad);
+    if (!offsets) return set_err(GCR_EINVAL, "%s: offsets is NULL", who);
+    if (!ctx) return set_err(GCR_EINVAL, "%s: null context", who);
+    if (npairs == 0) {
+        if (ms_kernel_out) *ms_kernel_out = 0.0;
+        return GCR_OK;
+    }
+    if (!pairs) return set_err(GCR_EINVAL, "%s: pairs is NULL", who);
+    if (!matches_out) return set_err(GCR_EINVAL, "%s: matches_out is NULL", who);
+    if (!ratios_out) return set_err(GCR_EINVAL, "%s: ratios_out is NULL", who);
+    if (!m_out) return set_err(GCR_EINVAL, "%s: m_out is NULL", who);
+    for (size_t k = 0; k < nsets; ++k) {
+        if (!sets[k]) return set_err(GCR_EINVAL, "%s: sets[%zu] is NULL", who, k);
+        if (sets[k]->ctx != ctx) return set_err(GCR_EINVAL, "%s: sets[%zu] was created on another context", who, k);
+    }
+    return guard([&]() -> int {
+        std::vector<MatchSetsPair> ps(npairs);
+        for (size_t k = 0; k < npairs; ++k) {
+            const uint32_t ia = pairs[2 * k], ib = pairs[2 * k + 1];
+            if (ia >= nsets || ib >= nsets)
+                return set_err(GCR_EINVAL, "%s: pairs[%zu] indexes past nsets = %zu", who, k, nsets);
+            if (sets[ia]->dim != sets[ib]->dim)
+                return set_err(GCR_EINVAL, "%s: the sets of pairs[%zu] differ in dim", who, k);
+            if (offsets[k + 1] < offsets[k] || offsets[k + 1] - offsets[k] < sets[ia]->n)
+                return set_err(GCR_EINVAL, "%s: offsets[%zu] leaves pair %zu fewer rows than its first set has", who,
+                               k + 1, k);
+            ps[k].a = sets[ia];
+            ps[k].b = sets[ib];
+            ps[k].mutual = opt->mutual;
+            ps[k].rule = rule;
+        }
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(match_sets_run(ctx->stream, ctx->n_cu, ctx->match_ws, ps.data(), npairs, offsets, matches_out, ratios_out,
+                            m_out, ms_kernel_out));
+        return GCR_OK;
+    });
+}
+
+int gcr_host_match_select(const uint32_t* idx, const uint32_t* dist, const uint32_t* idx2, const uint32_t* dist2,
+                          size_t n, const uint32_t* back, size_t nb, int guided, const gcr_match_options* opt,
+                          uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out) {
+    if (guided != 0 && guided != 1) return set_err(GCR_EINVAL, "match_select: guided must be 0 or 1");
+    MatchSelectRule rule{};
+    if (const char* bad = match_options_check(opt, guided != 0, &rule))
+        return set_err(GCR_EINVAL, "match_select: %s", bad);
+    if (const char* bad = match_select_check_args(idx, dist, idx2, dist2, n, back, nb, &rule, matches_out, ratios_out,
+                                                  cap, m_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    return guard([&]() -> int {
+        *m_out = host_match_select(idx, dist, idx2, dist2, n, back, nb, rule, matches_out, ratios_out);
+        return GCR_OK;
+    });
+}
+
+void gcr_match_select_tiling(uint32_t out[1]) {
+    if (out) out[0] = kMatchSelectRows;
+}
+
+int gcr_debug_match_workspace(gcr_ctx* ctx, uint64_t out[2]) {
+    if (!ctx) return set_err(GCR_EINVAL, "debug_match_workspace: null context");
+    if (!out) return set_err(GCR_EINVAL, "debug_match_workspace: out is NULL");
+    std::lock_guard<std::mutex> lk(ctx->match_ws.mu);
+    out[0] = ctx->match_ws.allocs;
+    out[1] = ctx->match_ws.dev_bytes;
+    return GCR_OK;
 }
 
 int gcr_host_grid_edges(const double* points, size_t n, int dims, const double* cell_size, uint64_t cell_number,

@@ -121,6 +121,27 @@ inline uint32_t match_plan(size_t n1, size_t n2, int n_cu, int pin, uint32_t* co
 }
 
 #if defined(__HIPCC__)
+// One search on device memory (match.hip): the plan, the launch and the merge.
+// Nothing here allocates, copies or synchronises.
+struct MatchDev {
+    const uint8_t* d1;          // n1 x dim, rows 16-byte aligned; no padding: every read is clamped by index
+    const uint8_t* d2;          // n2 x dim
+    const uint32_t* norm1;      // match_norms_enqueue's, n1
+    const uint32_t* norm2;      // n2
+    size_t n1, n2;
+    uint32_t dim;
+    uint32_t splits, cols;      // match_plan_env's
+    uint32_t* out[4];           // idx, dist, idx2, dist2: n1 each
+    uint32_t* part[4];          // [splits][n1] each; not read for splits == 1
+};
+// match_plan under GCR_MATCH_SPLIT=k (1 .. 1024, read per call): the number of column splits
+uint32_t match_plan_env(size_t n1, size_t n2, int n_cu, uint32_t* cols_out);
+// |row - 128|^2 of every row of d1 and of d2 (n2 may be 0) in one launch
+void match_norms_enqueue(hipStream_t stream, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim,
+                         uint32_t* norm1, uint32_t* norm2);
+// k_match<dim / 32>, then k_match_merge for splits > 1; errors through hipGetLastError
+void match_enqueue(hipStream_t stream, const MatchDev& m);
+
 // match.hip: uploads, runs the kernels on `stream`, downloads.  ms_kernel
 // (may be null): HIP-event time of the kernels alone.
 hipError_t match_device(hipStream_t stream, int n_cu, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2,

@@ -32,6 +32,10 @@
 //                  then writes the result itself.
 // Device memory beyond the descriptors: norms, results and the partials,
 // O(n1 * splits + n2).  The n1 x n2 matrix never exists.
+// The plan, the launches and the merge work on device pointers
+// (match_plan_env, match_norms_enqueue, match_enqueue): the array entry is
+// "allocate, upload, those, download, free", and the resident descriptor sets
+// (match_sets.hip) call the same functions on their own buffers.
 //
 // Guided matching (match_geo.h is the definition; gcr_match_descriptors_guided
 // the entry) adds two kernels and reuses k_match_norms and k_match_merge:
@@ -477,199 +481,203 @@ constexpr LaunchGeoFn kLaunchGeo[16] = {
 
 inline size_t up256(size_t v) { return (v + 255) & ~(size_t)255; }
 
+MatchArgs match_args(const MatchDev& m) {
+    MatchArgs a{};
+    a.d1 = m.d1;
+    a.d2 = m.d2;
+    a.norm1 = m.norm1;
+    a.norm2 = m.norm2;
+    a.n1 = (uint32_t)m.n1;
+    a.n2 = (uint32_t)m.n2;
+    a.splits = m.splits;
+    a.cols = m.cols;
+    a.idx = m.out[0];
+    a.dist = m.out[1];
+    a.idx2 = m.out[2];
+    a.dist2 = m.out[3];
+    const bool split = m.splits > 1;
+    a.p_idx = split ? m.part[0] : a.idx;
+    a.p_dist = split ? m.part[1] : a.dist;
+    a.p_idx2 = split ? m.part[2] : a.idx2;
+    a.p_dist2 = split ? m.part[3] : a.dist2;
+    return a;
+}
+
+// the array entries' one allocation: descriptors, norms, results and partials of one search
+struct MatchArrayBufs {
+    char* base = nullptr;
+    uint8_t *d1 = nullptr, *d2 = nullptr;
+    uint32_t *norm1 = nullptr, *norm2 = nullptr;
+    double* dbl[4] = {};        // guided: positions of image 1 and 2, terms of image 1 and 2
+};
+
+// `lead` doubles-first bytes (lead_b[4], 0 for the plain matcher), then MatchDev's buffers
+hipError_t match_array_alloc(MatchDev& m, const size_t lead_b[4], MatchArrayBufs& b) {
+    const size_t b_d1 = up256(m.n1 * m.dim), b_d2 = up256(m.n2 * m.dim);
+    const size_t b_n1 = up256(m.n1 * 4), b_n2 = up256(m.n2 * 4);
+    const size_t b_out = up256(m.n1 * 4), b_part = m.splits > 1 ? up256((size_t)m.splits * m.n1 * 4) : 0;
+    size_t lead = 0;
+    for (int k = 0; k < 4; ++k) lead += lead_b[k];
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b.base),
+                                   lead + b_d1 + b_d2 + b_n1 + b_n2 + 4 * b_out + 4 * b_part);
+    if (e != hipSuccess) return e;
+    char* p = b.base;                                     // the doubles first: 256-byte aligned either way
+    for (int k = 0; k < 4; ++k) {
+        b.dbl[k] = reinterpret_cast<double*>(p);
+        p += lead_b[k];
+    }
+    b.d1 = reinterpret_cast<uint8_t*>(p), p += b_d1;
+    b.d2 = reinterpret_cast<uint8_t*>(p), p += b_d2;
+    b.norm1 = reinterpret_cast<uint32_t*>(p), p += b_n1;
+    b.norm2 = reinterpret_cast<uint32_t*>(p), p += b_n2;
+    for (int k = 0; k < 4; ++k) m.out[k] = reinterpret_cast<uint32_t*>(p), p += b_out;
+    for (int k = 0; k < 4; ++k) m.part[k] = reinterpret_cast<uint32_t*>(p), p += b_part;
+    m.d1 = b.d1;
+    m.d2 = b.d2;
+    m.norm1 = b.norm1;
+    m.norm2 = b.norm2;
+    return hipSuccess;
+}
+
+// the four results to the host, the synchronisation, the event time, the free
+hipError_t match_array_finish(hipError_t e, hipStream_t stream, const MatchDev& m, MatchArrayBufs& b, hipEvent_t ev0,
+                              hipEvent_t ev1, uint32_t* const host_out[4], double* ms_kernel) {
+    if (e == hipSuccess) e = hipEventRecord(ev1, stream);
+    for (int k = 0; k < 4; ++k)
+        if (e == hipSuccess) e = hipMemcpyAsync(host_out[k], m.out[k], m.n1 * 4, hipMemcpyDeviceToHost, stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(stream);
+    if (e == hipSuccess && ms_kernel) {
+        float ms = 0.f;
+        e = hipEventElapsedTime(&ms, ev0, ev1);
+        *ms_kernel = (double)ms;
+    }
+    if (e != hipSuccess) (void)hipStreamSynchronize(stream);    // nothing in flight reads `base` past the free
+    if (ev0) (void)hipEventDestroy(ev0);
+    if (ev1) (void)hipEventDestroy(ev1);
+    (void)hipFree(b.base);
+    return e;
+}
+
 }  // namespace
 
-hipError_t match_device(hipStream_t stream, int n_cu, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2,
-                        uint32_t dim, uint32_t* idx, uint32_t* dist, uint32_t* idx2, uint32_t* dist2,
-                        double* ms_kernel) {
+uint32_t match_plan_env(size_t n1, size_t n2, int n_cu, uint32_t* cols_out) {
     // GCR_MATCH_SPLIT=k (1 .. 1024): pins the number of column splits (tests); read per call
     int pin = 0;
     if (const char* e = getenv("GCR_MATCH_SPLIT")) {
         const int v = atoi(e);
         if (v >= 1) pin = v < 1024 ? v : 1024;
     }
-    uint32_t cols = 0;
-    const uint32_t splits = match_plan(n1, n2, n_cu, pin, &cols);
-    const size_t row_blocks = (n1 + kMatchRowsPerWg - 1) / kMatchRowsPerWg;
+    return match_plan(n1, n2, n_cu, pin, cols_out);
+}
 
-    const size_t b_d1 = up256(n1 * dim), b_d2 = up256(n2 * dim);
-    const size_t b_n1 = up256(n1 * 4), b_n2 = up256(n2 * 4);
-    const size_t b_out = up256(n1 * 4), b_part = splits > 1 ? up256((size_t)splits * n1 * 4) : 0;
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base), b_d1 + b_d2 + b_n1 + b_n2 + 4 * b_out + 4 * b_part);
+void match_norms_enqueue(hipStream_t stream, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim,
+                         uint32_t* norm1, uint32_t* norm2) {
+    const uint32_t nb = (uint32_t)((n1 + n2 + kMatchThreads - 1) / kMatchThreads);
+    hipLaunchKernelGGL(k_match_norms, dim3(nb), dim3(kMatchThreads), 0, stream, d1, (uint32_t)n1, d2, (uint32_t)n2,
+                       dim, norm1, norm2);
+}
+
+void match_enqueue(hipStream_t stream, const MatchDev& m) {
+    const MatchArgs a = match_args(m);
+    const size_t row_blocks = (m.n1 + kMatchRowsPerWg - 1) / kMatchRowsPerWg;
+    kLaunch[m.dim / 32 - 1](a, (uint32_t)(row_blocks * m.splits), stream);
+    if (m.splits > 1)
+        hipLaunchKernelGGL(k_match_merge, dim3((uint32_t)((m.n1 + kMatchThreads - 1) / kMatchThreads)),
+                           dim3(kMatchThreads), 0, stream, a);
+}
+
+void match_geo_terms_enqueue(hipStream_t stream, const double* p1, size_t n1, const double* p2, size_t n2,
+                             const double* model, int kind, double* t1, double* t2) {
+    MatchGeoModel mdl;
+    for (int k = 0; k < 9; ++k) mdl.h[k] = model[k];
+    const uint32_t nb = (uint32_t)((n1 + n2 + kMatchThreads - 1) / kMatchThreads);
+    hipLaunchKernelGGL(k_match_geo_terms, dim3(nb), dim3(kMatchThreads), 0, stream, p1, (uint32_t)n1, p2, (uint32_t)n2,
+                       mdl, kind, t1, t2);
+}
+
+void match_geo_enqueue(hipStream_t stream, const MatchGeoDev& d) {
+    MatchGeoArgs g{};
+    g.m = match_args(d.m);
+    g.row_terms = d.row_terms;
+    g.col_terms = d.col_terms;
+    g.T = d.T;
+    g.kind = d.kind;
+    g.reverse = d.reverse;
+    const size_t row_blocks = (d.m.n1 + kMatchRowsPerWg - 1) / kMatchRowsPerWg;
+    kLaunchGeo[d.m.dim / 32 - 1](g, (uint32_t)(row_blocks * d.m.splits), stream);
+    if (d.m.splits > 1)
+        hipLaunchKernelGGL(k_match_merge, dim3((uint32_t)((d.m.n1 + kMatchThreads - 1) / kMatchThreads)),
+                           dim3(kMatchThreads), 0, stream, g.m);
+}
+
+// The array entry: allocate, upload, the device search, download, free.
+hipError_t match_device(hipStream_t stream, int n_cu, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2,
+                        uint32_t dim, uint32_t* idx, uint32_t* dist, uint32_t* idx2, uint32_t* dist2,
+                        double* ms_kernel) {
+    MatchDev m{};
+    m.n1 = n1;
+    m.n2 = n2;
+    m.dim = dim;
+    m.splits = match_plan_env(n1, n2, n_cu, &m.cols);
+    MatchArrayBufs b;
+    const size_t lead[4] = {0, 0, 0, 0};
+    hipError_t e = match_array_alloc(m, lead, b);
     if (e != hipSuccess) return e;
     hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    MatchArgs a{};
-    char* p = base;
-    a.d1 = reinterpret_cast<uint8_t*>(p), p += b_d1;
-    a.d2 = reinterpret_cast<uint8_t*>(p), p += b_d2;
-    uint32_t* norm1 = reinterpret_cast<uint32_t*>(p);
-    p += b_n1;
-    uint32_t* norm2 = reinterpret_cast<uint32_t*>(p);
-    p += b_n2;
-    a.norm1 = norm1;
-    a.norm2 = norm2;
-    a.idx = reinterpret_cast<uint32_t*>(p), p += b_out;
-    a.dist = reinterpret_cast<uint32_t*>(p), p += b_out;
-    a.idx2 = reinterpret_cast<uint32_t*>(p), p += b_out;
-    a.dist2 = reinterpret_cast<uint32_t*>(p), p += b_out;
-    if (splits > 1) {
-        a.p_idx = reinterpret_cast<uint32_t*>(p), p += b_part;
-        a.p_dist = reinterpret_cast<uint32_t*>(p), p += b_part;
-        a.p_idx2 = reinterpret_cast<uint32_t*>(p), p += b_part;
-        a.p_dist2 = reinterpret_cast<uint32_t*>(p), p += b_part;
-    } else {
-        a.p_idx = a.idx;
-        a.p_dist = a.dist;
-        a.p_idx2 = a.idx2;
-        a.p_dist2 = a.dist2;
-    }
-    a.n1 = (uint32_t)n1;
-    a.n2 = (uint32_t)n2;
-    a.splits = splits;
-    a.cols = cols;
-
     e = hipEventCreate(&ev0);
     if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(a.d1), d1, n1 * dim, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(a.d2), d2, n2 * dim, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d1, d1, n1 * dim, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d2, d2, n2 * dim, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipEventRecord(ev0, stream);
     if (e == hipSuccess) {
-        const uint32_t nb = (uint32_t)((n1 + n2 + kMatchThreads - 1) / kMatchThreads);
-        hipLaunchKernelGGL(k_match_norms, dim3(nb), dim3(kMatchThreads), 0, stream, a.d1, a.n1, a.d2, a.n2, dim,
-                           norm1, norm2);
-        kLaunch[dim / 32 - 1](a, (uint32_t)(row_blocks * splits), stream);
-        if (splits > 1)
-            hipLaunchKernelGGL(k_match_merge, dim3((uint32_t)((n1 + kMatchThreads - 1) / kMatchThreads)),
-                               dim3(kMatchThreads), 0, stream, a);
+        match_norms_enqueue(stream, b.d1, n1, b.d2, n2, dim, b.norm1, b.norm2);
+        match_enqueue(stream, m);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ev1, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx, a.idx, n1 * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dist, a.dist, n1 * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx2, a.idx2, n1 * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dist2, a.dist2, n1 * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e == hipSuccess && ms_kernel) {
-        float ms = 0.f;
-        e = hipEventElapsedTime(&ms, ev0, ev1);
-        *ms_kernel = (double)ms;
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(stream);    // nothing in flight reads `base` past the free
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipFree(base);
-    return e;
+    uint32_t* const host_out[4] = {idx, dist, idx2, dist2};
+    return match_array_finish(e, stream, m, b, ev0, ev1, host_out, ms_kernel);
 }
 
 hipError_t match_geo_device(hipStream_t stream, int n_cu, const uint8_t* d1, size_t n1, const double* p1,
                             const uint8_t* d2, size_t n2, const double* p2, uint32_t dim, int kind, const double* model,
                             double sq_threshold, int reverse, uint32_t* idx, uint32_t* dist, uint32_t* idx2,
                             uint32_t* dist2, double* ms_kernel) {
-    int pin = 0;                                          // GCR_MATCH_SPLIT, as match_device
-    if (const char* e = getenv("GCR_MATCH_SPLIT")) {
-        const int v = atoi(e);
-        if (v >= 1) pin = v < 1024 ? v : 1024;
-    }
     // the kernels' rows are the result rows, their columns the other image
-    const size_t nr = reverse ? n2 : n1, nc = reverse ? n1 : n2;
+    MatchGeoDev g{};
+    MatchDev& m = g.m;
+    m.n1 = reverse ? n2 : n1;
+    m.n2 = reverse ? n1 : n2;
+    m.dim = dim;
+    m.splits = match_plan_env(m.n1, m.n2, n_cu, &m.cols);
     const uint8_t* dr = reverse ? d2 : d1;
     const uint8_t* dc = reverse ? d1 : d2;
-    uint32_t cols = 0;
-    const uint32_t splits = match_plan(nr, nc, n_cu, pin, &cols);
-    const size_t row_blocks = (nr + kMatchRowsPerWg - 1) / kMatchRowsPerWg;
-
-    const size_t b_dr = up256(nr * dim), b_dc = up256(nc * dim);
-    const size_t b_nr = up256(nr * 4), b_nc = up256(nc * 4);
-    const size_t b_p1 = up256(n1 * 2 * sizeof(double)), b_p2 = up256(n2 * 2 * sizeof(double));
-    const size_t b_t1 = up256(n1 * kMatchGeoTerms * sizeof(double)), b_t2 = up256(n2 * kMatchGeoTerms * sizeof(double));
-    const size_t b_out = up256(nr * 4), b_part = splits > 1 ? up256((size_t)splits * nr * 4) : 0;
-    char* base = nullptr;
-    hipError_t e = hipMalloc(reinterpret_cast<void**>(&base),
-                             b_p1 + b_p2 + b_t1 + b_t2 + b_dr + b_dc + b_nr + b_nc + 4 * b_out + 4 * b_part);
+    MatchArrayBufs b;
+    const size_t lead[4] = {up256(n1 * 2 * sizeof(double)), up256(n2 * 2 * sizeof(double)),
+                            up256(n1 * kMatchGeoTerms * sizeof(double)), up256(n2 * kMatchGeoTerms * sizeof(double))};
+    hipError_t e = match_array_alloc(m, lead, b);
     if (e != hipSuccess) return e;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
-    MatchGeoArgs g{};
-    MatchArgs& a = g.m;
-    char* p = base;                                       // the doubles first: 256-byte aligned either way
-    double* dp1 = reinterpret_cast<double*>(p);
-    p += b_p1;
-    double* dp2 = reinterpret_cast<double*>(p);
-    p += b_p2;
-    double* t1 = reinterpret_cast<double*>(p);
-    p += b_t1;
-    double* t2 = reinterpret_cast<double*>(p);
-    p += b_t2;
-    a.d1 = reinterpret_cast<uint8_t*>(p), p += b_dr;
-    a.d2 = reinterpret_cast<uint8_t*>(p), p += b_dc;
-    uint32_t* norm1 = reinterpret_cast<uint32_t*>(p);
-    p += b_nr;
-    uint32_t* norm2 = reinterpret_cast<uint32_t*>(p);
-    p += b_nc;
-    a.norm1 = norm1;
-    a.norm2 = norm2;
-    a.idx = reinterpret_cast<uint32_t*>(p), p += b_out;
-    a.dist = reinterpret_cast<uint32_t*>(p), p += b_out;
-    a.idx2 = reinterpret_cast<uint32_t*>(p), p += b_out;
-    a.dist2 = reinterpret_cast<uint32_t*>(p), p += b_out;
-    if (splits > 1) {
-        a.p_idx = reinterpret_cast<uint32_t*>(p), p += b_part;
-        a.p_dist = reinterpret_cast<uint32_t*>(p), p += b_part;
-        a.p_idx2 = reinterpret_cast<uint32_t*>(p), p += b_part;
-        a.p_dist2 = reinterpret_cast<uint32_t*>(p), p += b_part;
-    } else {
-        a.p_idx = a.idx;
-        a.p_dist = a.dist;
-        a.p_idx2 = a.idx2;
-        a.p_dist2 = a.dist2;
-    }
-    a.n1 = (uint32_t)nr;
-    a.n2 = (uint32_t)nc;
-    a.splits = splits;
-    a.cols = cols;
+    double *dp1 = b.dbl[0], *dp2 = b.dbl[1], *t1 = b.dbl[2], *t2 = b.dbl[3];
     g.row_terms = reverse ? t2 : t1;
     g.col_terms = reverse ? t1 : t2;
     g.T = sq_threshold;
     g.kind = kind;
     g.reverse = reverse;
-    MatchGeoModel mdl;
-    for (int k = 0; k < 9; ++k) mdl.h[k] = model[k];
-
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     e = hipEventCreate(&ev0);
     if (e == hipSuccess) e = hipEventCreate(&ev1);
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(a.d1), dr, nr * dim, hipMemcpyHostToDevice, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(const_cast<uint8_t*>(a.d2), dc, nc * dim, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d1, dr, m.n1 * dim, hipMemcpyHostToDevice, stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(b.d2, dc, m.n2 * dim, hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dp1, p1, n1 * 2 * sizeof(double), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipMemcpyAsync(dp2, p2, n2 * 2 * sizeof(double), hipMemcpyHostToDevice, stream);
     if (e == hipSuccess) e = hipEventRecord(ev0, stream);
     if (e == hipSuccess) {
-        const uint32_t nb = (uint32_t)((n1 + n2 + kMatchThreads - 1) / kMatchThreads);
-        hipLaunchKernelGGL(k_match_norms, dim3(nb), dim3(kMatchThreads), 0, stream, a.d1, a.n1, a.d2, a.n2, dim,
-                           norm1, norm2);
-        hipLaunchKernelGGL(k_match_geo_terms, dim3(nb), dim3(kMatchThreads), 0, stream, dp1, (uint32_t)n1, dp2,
-                           (uint32_t)n2, mdl, kind, t1, t2);
-        kLaunchGeo[dim / 32 - 1](g, (uint32_t)(row_blocks * splits), stream);
-        if (splits > 1)
-            hipLaunchKernelGGL(k_match_merge, dim3((uint32_t)((nr + kMatchThreads - 1) / kMatchThreads)),
-                               dim3(kMatchThreads), 0, stream, a);
+        match_norms_enqueue(stream, b.d1, m.n1, b.d2, m.n2, dim, b.norm1, b.norm2);
+        match_geo_terms_enqueue(stream, dp1, n1, dp2, n2, model, kind, t1, t2);
+        match_geo_enqueue(stream, g);
         e = hipGetLastError();
     }
-    if (e == hipSuccess) e = hipEventRecord(ev1, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx, a.idx, nr * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dist, a.dist, nr * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(idx2, a.idx2, nr * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dist2, a.dist2, nr * 4, hipMemcpyDeviceToHost, stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-    if (e == hipSuccess && ms_kernel) {
-        float ms = 0.f;
-        e = hipEventElapsedTime(&ms, ev0, ev1);
-        *ms_kernel = (double)ms;
-    }
-    if (e != hipSuccess) (void)hipStreamSynchronize(stream);    // nothing in flight reads `base` past the free
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    (void)hipFree(base);
-    return e;
+    uint32_t* const host_out[4] = {idx, dist, idx2, dist2};
+    return match_array_finish(e, stream, m, b, ev0, ev1, host_out, ms_kernel);
 }
 
 }  // namespace gcr

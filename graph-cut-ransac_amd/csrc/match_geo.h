@@ -98,6 +98,18 @@ GCR_HD bool match_geo_adm(const double* one, const double* two, double T) {
     return match_geo_sq<KIND>(one, two) <= T;
 }
 
+// nullptr, or the message naming the first bad one of kind, model and sq_threshold
+// (the array entries and the resident sets' guided entry share it)
+inline const char* match_geo_check_model(int kind, const double* model, double sq_threshold) {
+    if (!model) return "match_descriptors_guided: model is NULL";
+    if (kind != kMatchGeoHomography && kind != kMatchGeoFundamental)
+        return "match_descriptors_guided: kind must be GCR_SOLVER_HOMOGRAPHY4 or GCR_SOLVER_FUNDAMENTAL7";
+    if (!(sq_threshold >= 0.0)) return "match_descriptors_guided: sq_threshold must be >= 0 (+inf allowed), not NaN";
+    for (int k = 0; k < 9; ++k)
+        if (!(__builtin_fabs(model[k]) <= DBL_MAX)) return "match_descriptors_guided: model has a non-finite entry";
+    return nullptr;
+}
+
 // nullptr, or the message naming the first bad argument
 inline const char* match_geo_check_args(const void* d1, size_t n1, const void* p1, const void* d2, size_t n2,
                                         const void* p2, uint32_t dim, int kind, const double* model,
@@ -106,12 +118,7 @@ inline const char* match_geo_check_args(const void* d1, size_t n1, const void* p
     if (const char* bad = match_check_args(d1, n1, d2, n2, dim, idx, dist, idx2, dist2)) return bad;
     if (!p1) return "match_descriptors_guided: p1 is NULL";
     if (!p2) return "match_descriptors_guided: p2 is NULL";
-    if (!model) return "match_descriptors_guided: model is NULL";
-    if (kind != kMatchGeoHomography && kind != kMatchGeoFundamental)
-        return "match_descriptors_guided: kind must be GCR_SOLVER_HOMOGRAPHY4 or GCR_SOLVER_FUNDAMENTAL7";
-    if (!(sq_threshold >= 0.0)) return "match_descriptors_guided: sq_threshold must be >= 0 (+inf allowed), not NaN";
-    for (int k = 0; k < 9; ++k)
-        if (!(__builtin_fabs(model[k]) <= DBL_MAX)) return "match_descriptors_guided: model has a non-finite entry";
+    if (const char* bad = match_geo_check_model(kind, model, sq_threshold)) return bad;
     if (reverse != 0 && reverse != 1) return "match_descriptors_guided: reverse must be 0 or 1";
     return nullptr;
 }
@@ -167,6 +174,22 @@ inline void host_match_rows_guided(const uint8_t* d1, size_t n1, const double* p
 }
 
 #if defined(__HIPCC__)
+// One guided search on device memory (match.hip), as MatchDev: m.d1 / norm1 /
+// n1 are the image of the RESULT rows (image 2 in reverse), m.d2 / norm2 / n2
+// the other image; the terms are match_geo_terms_enqueue's.
+struct MatchGeoDev {
+    MatchDev m;
+    const double* row_terms;    // [m.n1][kMatchGeoTerms]
+    const double* col_terms;    // [m.n2][kMatchGeoTerms]
+    double T;
+    int kind, reverse;
+};
+// the factorised residual's per-point terms of image 1 (p1, n1 -> t1) and image 2 (p2, n2 -> t2)
+void match_geo_terms_enqueue(hipStream_t stream, const double* p1, size_t n1, const double* p2, size_t n2,
+                             const double* model, int kind, double* t1, double* t2);
+// k_match_geo<dim / 32>, then k_match_merge for m.splits > 1
+void match_geo_enqueue(hipStream_t stream, const MatchGeoDev& g);
+
 // match.hip: uploads (descriptors, positions, model), runs the kernels on
 // `stream`, downloads n1 (forward) or n2 (reverse) results.  ms_kernel (may be
 // null): HIP-event time of the kernels alone.

@@ -123,6 +123,17 @@ class BatchItem(C.Structure):
     ]
 
 
+class MatchOptions(C.Structure):
+    """gcr_match_options: the front-end rule of the descriptor-set entries"""
+    _fields_ = [
+        ("has_ratio", C.c_int),
+        ("rr", C.c_double),
+        ("mutual", C.c_int),
+        ("has_max_distance", C.c_int),
+        ("max_distance", C.c_double),
+    ]
+
+
 # int (*)(void* user, const void* send, void* recv, size_t bytes)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
 
@@ -270,6 +281,20 @@ def _load():
                                                     C.c_double, C.c_int, C.c_int, vp, vp, vp, vp]
     L.gcr_match_tiling.argtypes = [u32p]
     L.gcr_match_tiling.restype = None
+    # resident descriptor sets (csrc/match_sets.h): matches (uint32 pairs) and ratios (doubles) out
+    mop, szp = C.POINTER(MatchOptions), C.POINTER(C.c_size_t)
+    L.gcr_descriptors_create.argtypes = [vp, vp, C.c_size_t, C.c_uint32, vp, C.POINTER(vp)]
+    L.gcr_descriptors_destroy.argtypes = [vp]
+    L.gcr_descriptors_destroy.restype = None
+    L.gcr_descriptors_info.argtypes = [vp, szp, u32p, C.POINTER(C.c_int)]
+    L.gcr_match_sets.argtypes = [vp, vp, vp, mop, vp, vp, C.c_size_t, szp, vp]
+    L.gcr_match_sets_guided.argtypes = [vp, vp, vp, C.c_int, vp, C.c_double, mop, vp, vp, C.c_size_t, szp, vp]
+    L.gcr_match_set_pairs.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, mop, vp, vp, vp, vp, vp]
+    L.gcr_host_match_select.argtypes = [vp, vp, vp, vp, C.c_size_t, vp, C.c_size_t, C.c_int, mop, vp, vp,
+                                        C.c_size_t, szp]
+    L.gcr_match_select_tiling.argtypes = [u32p]
+    L.gcr_match_select_tiling.restype = None
+    L.gcr_debug_match_workspace.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

@@ -16,6 +16,10 @@ mutual check.  `quantize_descriptors` brings float descriptors to uint8 and
 the same search among the pairs that agree with the estimated homography or
 fundamental matrix (gcr_match_descriptors_guided, csrc/match_geo.h);
 `fundamental_from_essential` brings an essential matrix to that form.
+`DescriptorSet` keeps one image's descriptors (and keypoints) on the device:
+`a.match(b)`, `a.match_guided(b, ...)` and `match_pairs` give the array
+functions' results without their uploads, with the ratio test, the mutual check
+and the row selection on the GPU too (csrc/match_sets.h, csrc/match_select.h).
 """
 from __future__ import annotations
 
@@ -23,7 +27,8 @@ import numpy as np
 
 __all__ = ["scale_features_from_sift", "orientation_features_from_sift", "keypoints_to_array", "perspective_warp",
            "warp_geometry", "BORDER_CONSTANT", "BORDER_REPLICATE", "match_descriptors", "quantize_descriptors",
-           "correspondences_from_matches", "match_descriptors_guided", "fundamental_from_essential"]
+           "correspondences_from_matches", "match_descriptors_guided", "fundamental_from_essential", "DescriptorSet",
+           "match_pairs"]
 
 # OpenCV's border codes (cv2.BORDER_CONSTANT = 0, cv2.BORDER_REPLICATE = 1)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
@@ -183,7 +188,10 @@ def match_descriptors(desc1, desc2, ratio=0.8, mutual=True, *, backend="gpu", de
     the arguments swapped, the same tie rule).  ``backend="gpu"`` runs the HIP
     kernels (csrc/match.hip: int8 matrix cores, exact), ``backend="host"`` the
     plain-loop definition on up to 16 threads, without a GPU; both give the
-    same bytes.
+    same bytes.  Binary descriptors (ORB, BRIEF) packed into bytes match in the
+    exact Hamming order as ``match_descriptors(np.unpackbits(a, axis=1),
+    np.unpackbits(b, axis=1))``: on 0 / 1 components the squared Euclidean
+    distance is the Hamming distance.
 
     Returns ``(matches, ratios)``: ``matches`` (M, 2) int64 rows (i, j) sorted
     by i, ``ratios`` (M,) float64 with sqrt(dist / dist2) (1.0 for 0 / 0 and
@@ -336,6 +344,219 @@ def match_descriptors_guided(desc1, desc2, kp1, kp2, model, kind, threshold, rat
     rows = np.nonzero(keep)[0]
     matches = np.stack([rows.astype(np.int64), idx[rows].astype(np.int64)], axis=1)
     return matches, ratios[rows]
+
+
+def _match_options(ratio, mutual, max_distance=None):
+    from . import _native as N
+
+    opt = N.MatchOptions()
+    opt.has_ratio = int(ratio is not None)
+    opt.rr = float(ratio) * float(ratio) if ratio is not None else 0.0
+    opt.mutual = int(bool(mutual))
+    opt.has_max_distance = int(max_distance is not None)
+    opt.max_distance = float(max_distance) if max_distance is not None else 0.0
+    return opt
+
+
+class DescriptorSet:
+    """One image's uint8 descriptors, resident on the GPU: uploaded once, with
+    their norms and, when ``keypoints`` are given, the keypoint positions.
+
+    ``desc`` is (n, dim) uint8 under ``match_descriptors``'s rules (n >= 1, dim
+    a multiple of 32 in 32..512).  ``keypoints`` are read as
+    ``match_descriptors_guided`` reads ``kp1``: one per descriptor row; they
+    are needed by ``match_guided`` only.  ``device`` as everywhere.
+
+    ``a.match(b)``, ``a.match_guided(b, ...)`` and ``match_pairs`` return what
+    ``match_descriptors`` / ``match_descriptors_guided`` return for the same
+    arrays, byte for byte, but the searches, the ratio test, the mutual check,
+    the ratios and the row selection all run on the device, and one download
+    of the matches ends the call: no descriptor crosses the bus again.  A set
+    can stand on either side of a match, against itself too, any number of
+    times.
+
+    ``len(s)`` is the row count; ``s.dim``, ``s.has_keypoints``.  ``close()``
+    frees the device memory (also at the end of a ``with`` block and on
+    garbage collection); a closed set raises ValueError when used."""
+
+    def __init__(self, desc, keypoints=None, *, device=None):
+        from . import _native as N
+
+        self._handle = None
+        d = _as_descriptors(desc, "desc")
+        if d.shape[1] % 32 or not 32 <= d.shape[1] <= 512:
+            raise ValueError(f"the descriptor dimension must be a multiple of 32 in 32..512, got {d.shape[1]}")
+        if d.shape[0] == 0:
+            raise ValueError("desc needs at least one row")
+        p = None
+        if keypoints is not None:
+            p = _positions(keypoints, "keypoints")
+            if len(p) != len(d):
+                raise ValueError(f"one keypoint per descriptor: keypoints has {len(p)} rows for {len(d)} descriptors")
+        import ctypes as C
+
+        self._n, self._dim, self._has_kp = int(d.shape[0]), int(d.shape[1]), p is not None
+        self._ctx = N.context(device)                     # the context outlives the set: kept for the process
+        out = C.c_void_p()
+        N.check(N.lib.gcr_descriptors_create(self._ctx, d.ctypes.data, self._n, self._dim,
+                                             None if p is None else p.ctypes.data, C.byref(out)))
+        self._handle = out.value
+
+    def __len__(self):
+        return self._n
+
+    @property
+    def dim(self) -> int:
+        return self._dim
+
+    @property
+    def has_keypoints(self) -> bool:
+        return self._has_kp
+
+    @property
+    def closed(self) -> bool:
+        return self._handle is None
+
+    def close(self) -> None:
+        h, self._handle = self._handle, None
+        if h is not None:
+            from . import _native as N
+
+            N.lib.gcr_descriptors_destroy(h)
+
+    def __enter__(self):
+        self._open()
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _open(self):
+        if self._handle is None:
+            raise ValueError("the DescriptorSet is closed")
+        return self._handle
+
+    def _pair(self, other):
+        """the two handles, after the checks every match of two sets makes"""
+        if not isinstance(other, DescriptorSet):
+            raise ValueError(f"a DescriptorSet matches another DescriptorSet, got {type(other).__name__}")
+        ha, hb = self._open(), other._open()
+        if self._dim != other._dim:
+            raise ValueError(f"desc1 and desc2 differ in dimension: {self._dim} and {other._dim}")
+        if self._ctx != other._ctx:
+            raise ValueError("the two DescriptorSets live on different devices")
+        return ha, hb
+
+    def _run(self, call):
+        """call(matches_ptr, ratios_ptr, cap, m_ptr) -> the (matches, ratios) tuple"""
+        import ctypes as C
+
+        from . import _native as N
+
+        matches = np.empty((self._n, 2), dtype=np.uint32)
+        ratios = np.empty(self._n, dtype=np.float64)
+        m = C.c_size_t()
+        N.check(call(matches.ctypes.data, ratios.ctypes.data, self._n, C.byref(m)))
+        return matches[:m.value].astype(np.int64), ratios[:m.value].copy()
+
+    def match(self, other, ratio=0.8, mutual=True):
+        """``match_descriptors(desc_self, desc_other, ratio, mutual)`` on the two
+        resident sets: the same rules, the same ``(matches, ratios)``."""
+        from . import _native as N
+
+        ha, hb = self._pair(other)
+        if ratio is not None and not (np.isfinite(ratio) and ratio > 0):
+            raise ValueError("ratio must be None or a finite number > 0")
+        opt = _match_options(ratio, mutual)
+        return self._run(lambda mp, rp, cap, m: N.lib.gcr_match_sets(self._ctx, ha, hb, opt, mp, rp, cap, m, None))
+
+    def match_guided(self, other, model, kind, threshold, ratio=None, mutual=True, max_distance=None):
+        """``match_descriptors_guided(desc_self, desc_other, kp_self, kp_other,
+        model, kind, threshold, ratio, mutual, max_distance)`` on the two
+        resident sets; both need keypoints."""
+        from . import _native as N
+
+        ha, hb = self._pair(other)
+        if kind not in _GUIDED_KINDS:
+            raise ValueError(f"kind must be 'homography' or 'fundamental', got {kind!r}")
+        if not (self._has_kp and other._has_kp):
+            raise ValueError("match_guided needs keypoints on both DescriptorSets")
+        m = np.asarray(model, dtype=np.float64)
+        if m.shape != (3, 3) or not np.isfinite(m).all():
+            raise ValueError("model must be a finite 3 x 3 matrix")
+        m = np.ascontiguousarray(m)
+        if not (np.isfinite(threshold) and threshold > 0):
+            raise ValueError("threshold must be a finite number of pixels > 0")
+        if ratio is not None and not (np.isfinite(ratio) and ratio > 0):
+            raise ValueError("ratio must be None or a finite number > 0")
+        if max_distance is not None and not max_distance >= 0:
+            raise ValueError("max_distance must be None or a number >= 0")
+        T = float(threshold) * float(threshold)
+        opt = _match_options(ratio, mutual, max_distance)
+        code = _GUIDED_KINDS[kind]
+        return self._run(lambda mp, rp, cap, mo: N.lib.gcr_match_sets_guided(self._ctx, ha, hb, code, m.ctypes.data, T,
+                                                                             opt, mp, rp, cap, mo, None))
+
+
+def match_pairs(sets, pairs, ratio=0.8, mutual=True):
+    """``a.match(b, ratio, mutual)`` for many pairs of resident sets in one
+    call: every pair is queued on the device, then one synchronisation and one
+    download.  ``sets`` is a sequence of ``DescriptorSet`` on one device,
+    ``pairs`` a sequence of index pairs (ia, ib) into it, the row side first; a
+    set may appear in any number of pairs, on either side, and with itself.
+
+    Returns a list of ``(matches, ratios)`` tuples, one per pair in the order
+    of ``pairs``, each equal to ``sets[ia].match(sets[ib], ratio, mutual)``.
+    An empty ``pairs`` gives ``[]``."""
+    import ctypes as C
+
+    from . import _native as N
+
+    sets = list(sets)
+    for s in sets:
+        if not isinstance(s, DescriptorSet):
+            raise ValueError(f"sets must hold DescriptorSets, got {type(s).__name__}")
+    pr = np.asarray(pairs)
+    if pr.size == 0:
+        pr = np.zeros((0, 2), dtype=np.int64)
+    if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+        raise ValueError("pairs must be a sequence of integer pairs (ia, ib)")
+    if pr.size and (pr.min() < 0 or pr.max() >= len(sets)):
+        raise ValueError(f"pairs index past the {len(sets)} sets")
+    if ratio is not None and not (np.isfinite(ratio) and ratio > 0):
+        raise ValueError("ratio must be None or a finite number > 0")
+    handles = [s._open() for s in sets]
+    if len(pr) == 0:
+        return []
+    for ia, ib in pr.tolist():
+        if sets[ia].dim != sets[ib].dim:
+            raise ValueError(f"desc1 and desc2 differ in dimension: {sets[ia].dim} and {sets[ib].dim}")
+    if len({s._ctx for s in sets}) != 1:
+        raise ValueError("the DescriptorSets live on different devices")
+    pr32 = np.ascontiguousarray(pr, dtype=np.uint32)
+    rows = np.array([len(sets[ia]) for ia in pr[:, 0].tolist()], dtype=np.uint64)
+    offsets = np.zeros(len(pr) + 1, dtype=np.uintp)
+    offsets[1:] = np.cumsum(rows)
+    total = int(offsets[-1])
+    matches = np.empty((total, 2), dtype=np.uint32)
+    ratios = np.empty(total, dtype=np.float64)
+    counts = np.zeros(len(pr), dtype=np.uintp)
+    hs = (C.c_void_p * len(handles))(*handles)
+    N.check(N.lib.gcr_match_set_pairs(sets[0]._ctx, C.addressof(hs), len(handles), pr32.ctypes.data, len(pr),
+                                      _match_options(ratio, mutual), matches.ctypes.data, ratios.ctypes.data,
+                                      offsets.ctypes.data, counts.ctypes.data, None))
+    out = []
+    for k in range(len(pr)):
+        lo, m = int(offsets[k]), int(counts[k])
+        out.append((matches[lo:lo + m].astype(np.int64), ratios[lo:lo + m].copy()))
+    return out
 
 
 def fundamental_from_essential(E, K1, K2) -> np.ndarray:

@@ -795,6 +795,75 @@ int gcr_host_match_descriptors_guided(const uint8_t* d1, size_t n1, const double
  * workgroup, out[1] = rows of d2 (columns) per step, out[2] = the least
  * columns per split the planner chooses */
 void gcr_match_tiling(uint32_t out[3]);
+
+/* Resident descriptor sets (csrc/match_sets.h): one image's descriptors on the
+ * device, uploaded once with their norms and, optionally, the keypoint
+ * positions.  Two sets are matched entirely on the device: the forward and
+ * (mutual) the reverse search by the kernels of gcr_match_descriptors /
+ * gcr_match_descriptors_guided, then csrc/match_select.h's rule -- the ratio
+ * test, the distance cap, the mutual check, the ratios -- and an ordered
+ * compaction of the kept rows; one synchronisation and one download end the
+ * call.  The results are what the Python front end (features.match_descriptors,
+ * features.match_descriptors_guided) computes from the array entries' outputs,
+ * bit for bit.  What a call needs beyond the sets lives in a workspace of the
+ * context that grows when a call needs more and is freed with the context: a
+ * call whose shapes fit allocates nothing. */
+typedef struct gcr_descriptors gcr_descriptors;
+
+typedef struct gcr_match_options {
+    int has_ratio;             /* 0: no ratio test */
+    double rr;                 /* ratio * ratio, finite and > 0 */
+    int mutual;                /* 0 or 1: keep (i, j) only if i is j's first neighbour too */
+    int has_max_distance;      /* guided entries only; 0: no cap */
+    double max_distance;       /* keep only dist <= max_distance; >= 0 */
+} gcr_match_options;
+
+/* d is n x dim uint8 under gcr_match_descriptors' ranges; positions is NULL or
+ * n x 2 finite doubles (x, y).  A NULL argument, a bad n or dim, a non-finite
+ * position: GCR_EINVAL naming the argument, before any GPU work.  The set
+ * belongs to ctx and must be destroyed before it. */
+int gcr_descriptors_create(gcr_ctx* ctx, const uint8_t* d, size_t n, uint32_t dim, const double* positions,
+                           gcr_descriptors** out);
+void gcr_descriptors_destroy(gcr_descriptors* set);     /* safe on NULL */
+int gcr_descriptors_info(const gcr_descriptors* set, size_t* n_out, uint32_t* dim_out, int* has_positions_out);
+/* The rows of `a` matched against `b` (which may be `a`).  matches_out takes
+ * cap x 2 values, the pairs (i, j) in ascending i, ratios_out cap doubles,
+ * sqrt(dist / dist2) or 1.0; *m_out their count.  cap must be at least a's row
+ * count: nothing is ever truncated.  ms_kernel_out may be NULL; else FOUR
+ * doubles of HIP-event times in ms: all kernels, the forward search, the
+ * reverse search, the select launches.  GCR_EINVAL naming the argument for a
+ * NULL argument, a set of another context, sets of different dim, a bad option. */
+int gcr_match_sets(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, const gcr_match_options* opt,
+                   uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out, double* ms_kernel_out);
+/* The same among the pairs `model` admits (kind, model, sq_threshold as
+ * gcr_match_descriptors_guided checks them); both sets need positions.  A row
+ * without an admissible candidate gives no match; one with a single candidate
+ * passes the ratio test. */
+int gcr_match_sets_guided(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, int kind,
+                          const double* model, double sq_threshold, const gcr_match_options* opt,
+                          uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out,
+                          double* ms_kernel_out);
+/* gcr_match_sets over many pairs in one call: pairs is npairs x 2 indices into
+ * sets (first the row side); every pair is queued, then one synchronisation
+ * and one download.  offsets (npairs + 1, ascending) places pair p's rows at
+ * matches_out + 2 * offsets[p] and ratios_out + offsets[p]; offsets[p + 1] -
+ * offsets[p] must be at least the row count of the pair's first set.  m_out
+ * takes npairs counts.  ms_kernel_out may be NULL; else ONE double, all
+ * kernels.  npairs == 0 is valid and does nothing. */
+int gcr_match_set_pairs(gcr_ctx* ctx, const gcr_descriptors* const* sets, size_t nsets, const uint32_t* pairs,
+                        size_t npairs, const gcr_match_options* opt, uint32_t* matches_out, double* ratios_out,
+                        const size_t* offsets, size_t* m_out, double* ms_kernel_out);
+/* host-only: csrc/match_select.h's rule by plain loops on a search's results
+ * (n rows).  back is NULL (no mutual check) or the reverse search's idx (nb
+ * values).  guided selects the guided variant of the rule. */
+int gcr_host_match_select(const uint32_t* idx, const uint32_t* dist, const uint32_t* idx2, const uint32_t* dist2,
+                          size_t n, const uint32_t* back, size_t nb, int guided, const gcr_match_options* opt,
+                          uint32_t* matches_out, double* ratios_out, size_t cap, size_t* m_out);
+/* the select kernels' tiling, for tests at its edges: out[0] = rows per workgroup */
+void gcr_match_select_tiling(uint32_t out[1]);
+/* out[0] = device allocations made so far for ctx's matching workspace (a set's
+ * own buffers are not counted), out[1] = the workspace's device bytes held now */
+int gcr_debug_match_workspace(gcr_ctx* ctx, uint64_t out[2]);
 /* measurement (bench.py): achievable HBM bandwidth of the device, GB/s of
  * read + write traffic of a streaming device-to-device copy of `bytes` bytes,
  * best of `iters` timed copies of each of two variants, plain and nontemporal

@@ -25,6 +25,18 @@ share of the pairs, and the share of the kernel's 32 x 32 tiles and of its
 128-row x 64-column steps without an admissible pair (numpy, from the
 definition), which the kernel skips.
 
+With --sets only the resident-set legs run (features.DescriptorSet) on
+problem_match(n, 0.4 n): the array call match_descriptors(ratio=0.8,
+mutual=True), the set call a.match(b) with both sets resident (with the pinned
+and, under GCR_MATCH_SETS_PAGEABLE=1, the pageable download), set creation on
+its own, the C entry with its HIP-event breakdown (forward search, reverse
+search, select launches), the same for match_guided under H_GT and F against
+match_descriptors_guided, and match_pairs over --pair-sets sets of 2 000 ..
+10 000 rows in all unordered pairs against a loop of array calls and a loop of
+a.match(b).  The legs of a group alternate call by call; medians of --calls
+after a warm-up, quartiles beside them; every set result is compared with the
+array function's byte for byte.
+
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -48,6 +60,9 @@ ap.add_argument("--splits", default="0,1,2,4,7,16", help="column splits to time 
 ap.add_argument("--no-pipeline", action="store_true")
 ap.add_argument("--guided", action="store_true", help="the guided matcher's legs only")
 ap.add_argument("--threshold", type=float, default=3.0, help="guided: the bound in pixels")
+ap.add_argument("--sets", action="store_true", help="the resident descriptor sets' legs only")
+ap.add_argument("--pair-sets", type=int, default=16, help="sets: the number of sets of the match_pairs leg")
+ap.add_argument("--pair-calls", type=int, default=5, help="sets: timed repetitions of the match_pairs legs")
 args = ap.parse_args()
 
 sys.path.insert(0, args.pkg)
@@ -173,8 +188,143 @@ def guided_mode():
     print(json.dumps(out))
 
 
+# ---- sets mode -----------------------------------------------------------------
+def timed(fn):
+    t0 = time.perf_counter()
+    r = fn()
+    return (time.perf_counter() - t0) * 1e3, r
+
+
+def alternate(legs, calls):
+    """name -> list of ms; call -1 warms up; the legs alternate call by call.  Also the last results."""
+    acc, last = {name: [] for name in legs}, {}
+    for k in range(-1, calls):
+        for name, fn in legs.items():
+            ms, last[name] = timed(fn)
+            if k >= 0:
+                acc[name].append(ms)
+    return acc, last
+
+
+def same(a, b):
+    return bool(a[0].dtype == b[0].dtype and np.array_equal(a[0], b[0]) and a[1].tobytes() == b[1].tobytes())
+
+
+def sets_mode():
+    kp1, e1, kp2, e2, pairs, Hgt = S.problem_match(n, int(0.4 * n), seed=SEED, dim=dim)
+    e = (2.0 * S.IMG_W, S.IMG_H / 2.0, 1.0)
+    skew = np.array([[0.0, -e[2], e[1]], [e[2], 0.0, -e[0]], [-e[1], e[0], 0.0]])
+    models = {"H": ("homography", np.ascontiguousarray(Hgt)), "F": ("fundamental", np.ascontiguousarray(skew @ Hgt))}
+    a, b = F.DescriptorSet(e1, kp1), F.DescriptorSet(e2, kp2)
+    g = {}
+
+    def pageable():
+        os.environ["GCR_MATCH_SETS_PAGEABLE"] = "1"
+        try:
+            return a.match(b)
+        finally:
+            os.environ.pop("GCR_MATCH_SETS_PAGEABLE", None)
+
+    def create():
+        F.DescriptorSet(e1, kp1).close()
+
+    # the C entry with its event breakdown (four doubles) and without events
+    mbuf, rbuf, mo = np.empty((n, 2), np.uint32), np.empty(n), C.c_size_t()
+    opt = F._match_options(0.8, True)
+    ms4 = np.zeros(4)
+    events = []
+
+    def c_entry_events():
+        N.check(N.lib.gcr_match_sets(ctx, a._handle, b._handle, opt, mbuf.ctypes.data, rbuf.ctypes.data, n,
+                                     C.byref(mo), ms4.ctypes.data))
+        events.append(ms4.copy())
+
+    def c_entry():
+        N.check(N.lib.gcr_match_sets(ctx, a._handle, b._handle, opt, mbuf.ctypes.data, rbuf.ctypes.data, n,
+                                     C.byref(mo), None))
+
+    # three groups, each alternating call by call: the array call frees its buffers at its end, which the
+    # call after it pays for, so the set call is timed both right after an array call and among set calls only
+    acc, last = alternate({"array_call": lambda: F.match_descriptors(e1, e2, ratio=0.8, mutual=True),
+                           "set_call": lambda: a.match(b)}, args.calls)
+    acc2, last2 = alternate({"set_call_among_set_calls": lambda: a.match(b),
+                             "set_call_pageable_download": pageable,
+                             "set_c_entry": c_entry,
+                             "set_c_entry_with_events": c_entry_events}, args.calls)
+    acc3, _ = alternate({"set_create": create}, args.calls)
+    acc.update(acc2)
+    acc.update(acc3)
+    last.update(last2)
+    g["match"] = {name: quart(v) for name, v in acc.items()}
+    ev = np.array(events[1:])                             # without the warm-up call
+    g["match"]["kernels"] = {name: quart(ev[:, k].tolist()) for k, name in
+                             enumerate(("all", "forward_search", "reverse_search", "select_launches"))}
+    med = lambda name: g["match"][name]["median_ms"]
+    g["match"]["set_over_array"] = round(med("set_call") / med("array_call"), 4)
+    g["match"]["set_call_not_above_array_call"] = med("set_call") <= med("array_call")
+    g["match"]["c_entry_minus_kernels_ms"] = round(med("set_c_entry") - g["match"]["kernels"]["all"]["median_ms"], 4)
+    g["match"]["python_over_c_entry_ms"] = round(med("set_call") - med("set_c_entry"), 4)
+    g["match"]["matches"] = len(last["set_call"][0])
+    g["match"]["equal_bytes"] = same(last["set_call"], last["array_call"]) and \
+        same(last["set_call_pageable_download"], last["array_call"])
+    g["match"]["workspace"] = list(map(int, workspace()))
+
+    for k, (kind, model) in models.items():
+        acc, last = alternate({
+            "array_call": lambda: F.match_descriptors_guided(e1, e2, kp1, kp2, model, kind, args.threshold),
+            "set_call": lambda: a.match_guided(b, model, kind, args.threshold)}, args.calls)
+        g[f"guided_{k}"] = {name: quart(v) for name, v in acc.items()}
+        code = {"homography": 3, "fundamental": 4}[kind]
+        gopt = F._match_options(None, True)
+        ev = []
+        for _ in range(args.calls + 1):
+            N.check(N.lib.gcr_match_sets_guided(ctx, a._handle, b._handle, code, model.ctypes.data,
+                                                args.threshold * args.threshold, gopt, mbuf.ctypes.data,
+                                                rbuf.ctypes.data, n, C.byref(mo), ms4.ctypes.data))
+            ev.append(ms4.copy())
+        ev = np.array(ev[1:])
+        g[f"guided_{k}"]["kernels"] = {name: quart(ev[:, q].tolist()) for q, name in
+                                       enumerate(("all", "forward_search", "reverse_search", "select_launches"))}
+        sm, am = g[f"guided_{k}"]["set_call"]["median_ms"], g[f"guided_{k}"]["array_call"]["median_ms"]
+        g[f"guided_{k}"].update({"set_over_array": round(sm / am, 4), "set_call_not_above_array_call": sm <= am,
+                                 "matches": len(last["set_call"][0]),
+                                 "equal_bytes": same(last["set_call"], last["array_call"])})
+    a.close()
+    b.close()
+
+    # match_pairs: sets of 2 000 .. 10 000 rows, every unordered pair
+    ns = np.linspace(2000, 10000, args.pair_sets).astype(int).tolist()
+    prng = np.random.default_rng(SEED + 1)
+    ds = [prng.integers(0, 256, (k, dim), dtype=np.uint8) for k in ns]
+    sets = [F.DescriptorSet(d) for d in ds]
+    pr = [(i, j) for i in range(len(ns)) for j in range(i + 1, len(ns))]
+    acc, last = alternate({
+        "array_loop": lambda: [F.match_descriptors(ds[i], ds[j], ratio=0.8, mutual=True) for i, j in pr],
+        "set_loop": lambda: [sets[i].match(sets[j]) for i, j in pr],
+        "match_pairs": lambda: F.match_pairs(sets, pr)}, args.pair_calls)
+    g["pairs"] = {name: {**quart(v), "pairs_per_s": round(len(pr) / (statistics.median(v) * 1e-3), 1)}
+                  for name, v in acc.items()}
+    g["pairs"].update({"sets": len(ns), "rows": ns, "pairs": len(pr),
+                       "equal_bytes": all(same(x, y) and same(x, z) for x, y, z in
+                                          zip(last["match_pairs"], last["set_loop"], last["array_loop"])),
+                       "workspace": list(map(int, workspace()))})
+    for s_ in sets:
+        s_.close()
+    out["sets"] = g
+    print(json.dumps(out))
+
+
+def workspace():
+    w = (C.c_uint64 * 2)()
+    N.check(N.lib.gcr_debug_match_workspace(ctx, w))
+    return w[0], w[1]
+
+
 if args.guided:
     guided_mode()
+    sys.exit(0)
+if args.sets:
+    sets_mode()
     sys.exit(0)
 
 # ---- leg 1 ---------------------------------------------------------------------
