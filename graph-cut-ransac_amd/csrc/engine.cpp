@@ -64,6 +64,7 @@
 #include "match.h"
 #include "match_geo.h"
 #include "match_select.h"
+#include "match_knn.h"
 #include "match_sets.h"
 
 using namespace gcr;
@@ -6733,6 +6734,55 @@ int gcr_match_set_pairs(gcr_ctx* ctx, const gcr_descriptors* const* sets, size_t
         HIPC(hipSetDevice(ctx->device));
         HIPC(match_sets_run(ctx->stream, ctx->n_cu, ctx->match_ws, ps.data(), npairs, offsets, matches_out, ratios_out,
                             m_out, ms_kernel_out));
+        return GCR_OK;
+    });
+}
+
+// ------------------------------------------------------ k nearest neighbours --
+int gcr_knn_descriptors(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim,
+                        uint32_t k, uint32_t* idx_out, uint32_t* dist_out, double* ms_kernel_out) {
+    if (const char* bad = knn_check_args(d1, n1, d2, n2, dim, k, idx_out, dist_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    if (!ctx) return set_err(GCR_EINVAL, "null context");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(knn_device(ctx->stream, ctx->n_cu, d1, n1, d2, n2, dim, k, idx_out, dist_out, ms_kernel_out));
+        return GCR_OK;
+    });
+}
+
+int gcr_host_knn_descriptors(const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim, uint32_t k,
+                             int threads, uint32_t* idx_out, uint32_t* dist_out) {
+    if (const char* bad = knn_check_args(d1, n1, d2, n2, dim, k, idx_out, dist_out))
+        return set_err(GCR_EINVAL, "%s", bad);
+    return guard([&]() -> int {
+        const size_t nt = std::min<size_t>(n1, (size_t)std::max(1, std::min(threads, 64)));
+        const size_t step = (n1 + nt - 1) / nt;
+        std::vector<std::thread> pool;
+        for (size_t t = 1; t < nt; ++t)
+            pool.emplace_back([=] {
+                host_knn_rows(d1, d2, n2, dim, k, std::min(n1, t * step), std::min(n1, (t + 1) * step), idx_out,
+                              dist_out);
+            });
+        host_knn_rows(d1, d2, n2, dim, k, 0, std::min(n1, step), idx_out, dist_out);
+        for (auto& th : pool) th.join();
+        return GCR_OK;
+    });
+}
+
+int gcr_knn_sets(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, uint32_t k, uint32_t* idx_out,
+                 uint32_t* dist_out, double* ms_kernel_out) {
+    // the checks that need no context first: they are reachable without a GPU
+    if (!a) return set_err(GCR_EINVAL, "knn_sets: a is NULL");
+    if (!b) return set_err(GCR_EINVAL, "knn_sets: b is NULL");
+    if (!idx_out) return set_err(GCR_EINVAL, "knn_sets: idx_out is NULL");
+    if (!dist_out) return set_err(GCR_EINVAL, "knn_sets: dist_out is NULL");
+    if (k == 0 || k > kKnnMaxK) return set_err(GCR_EINVAL, "knn_sets: k must be in 1 .. 8");
+    if (!ctx) return set_err(GCR_EINVAL, "knn_sets: null context");
+    if (const char* bad = match_set_pair_check(ctx, a, b)) return set_err(GCR_EINVAL, "knn_sets: %s", bad);
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        HIPC(knn_sets_run(ctx->stream, ctx->n_cu, ctx->match_ws, a, b, k, idx_out, dist_out, ms_kernel_out));
         return GCR_OK;
     });
 }

@@ -69,6 +69,11 @@ void match_set_destroy(gcr_descriptors* s);
 hipError_t match_sets_run(hipStream_t stream, int n_cu, MatchWorkspace& ws, const MatchSetsPair* pairs, size_t npairs,
                           const size_t* offsets, uint32_t* matches_out, double* ratios_out, size_t* m_out, double* ms);
 
+// The device block to at least dev_need bytes and the download's staging
+// (pinned, or ws.pageable) to host_need; a device block that has to grow waits
+// for the stream first.  The caller holds ws.mu.
+hipError_t match_workspace_grow(hipStream_t stream, MatchWorkspace& ws, size_t dev_need, size_t host_need,
+                                bool pageable);
 void match_workspace_free(MatchWorkspace& ws);
 
 }  // namespace gcr

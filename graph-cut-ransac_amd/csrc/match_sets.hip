@@ -223,7 +223,10 @@ void enqueue_select(hipStream_t stream, const MatchSetsPair& p, const PairBufs& 
     hipLaunchKernelGGL(k_match_select_scatter, dim3(nwg), dim3(kSelThreads), 0, stream, a);
 }
 
-hipError_t grow(hipStream_t stream, MatchWorkspace& ws, size_t dev_need, size_t host_need, bool pageable) {
+}  // namespace
+
+hipError_t match_workspace_grow(hipStream_t stream, MatchWorkspace& ws, size_t dev_need, size_t host_need,
+                                bool pageable) {
     if (dev_need > ws.dev_bytes) {
         hipError_t e = hipStreamSynchronize(stream);      // nothing of an earlier call reads the old block
         if (e != hipSuccess) return e;
@@ -247,8 +250,6 @@ hipError_t grow(hipStream_t stream, MatchWorkspace& ws, size_t dev_need, size_t 
     }
     return hipSuccess;
 }
-
-}  // namespace
 
 hipError_t match_set_create(hipStream_t stream, const uint8_t* d, size_t n, uint32_t dim, const double* positions,
                             gcr_descriptors* out) {
@@ -326,7 +327,7 @@ hipError_t match_sets_run(hipStream_t stream, int n_cu, MatchWorkspace& ws, cons
     (void)out_measure.take<double>(total);
     const size_t out_bytes = out_measure.used;
 
-    hipError_t e = grow(stream, ws, scratch + out_bytes, out_bytes, pageable);
+    hipError_t e = match_workspace_grow(stream, ws, scratch + out_bytes, out_bytes, pageable);
     if (e != hipSuccess) return e;
     const bool timed = ms != nullptr;
     const bool phases = timed && npairs == 1;

@@ -295,6 +295,10 @@ def _load():
     L.gcr_match_select_tiling.argtypes = [u32p]
     L.gcr_match_select_tiling.restype = None
     L.gcr_debug_match_workspace.argtypes = [vp, C.POINTER(C.c_uint64)]
+    # k nearest neighbours (csrc/match_knn.h): idx / dist (uint32, n1 x k) out
+    L.gcr_knn_descriptors.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, dp]
+    L.gcr_host_knn_descriptors.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, vp, vp]
+    L.gcr_knn_sets.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, dp]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

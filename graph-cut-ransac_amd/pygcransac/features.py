@@ -20,6 +20,11 @@ fundamental matrix (gcr_match_descriptors_guided, csrc/match_geo.h);
 `a.match(b)`, `a.match_guided(b, ...)` and `match_pairs` give the array
 functions' results without their uploads, with the ratio test, the mutual check
 and the row selection on the GPU too (csrc/match_sets.h, csrc/match_select.h).
+`knn_descriptors` (and `DescriptorSet.knn`) return every row's k nearest
+neighbours (gcr_knn_descriptors, csrc/match_knn.h) and `matches_from_knn` turns
+them into one-to-many matches: on repeated structure, where the second
+neighbour is another copy of the true one, the ratio test moves to the end of
+the group of equally good candidates.
 """
 from __future__ import annotations
 
@@ -28,7 +33,7 @@ import numpy as np
 __all__ = ["scale_features_from_sift", "orientation_features_from_sift", "keypoints_to_array", "perspective_warp",
            "warp_geometry", "BORDER_CONSTANT", "BORDER_REPLICATE", "match_descriptors", "quantize_descriptors",
            "correspondences_from_matches", "match_descriptors_guided", "fundamental_from_essential", "DescriptorSet",
-           "match_pairs"]
+           "match_pairs", "knn_descriptors", "matches_from_knn"]
 
 # OpenCV's border codes (cv2.BORDER_CONSTANT = 0, cv2.BORDER_REPLICATE = 1)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
@@ -227,6 +232,112 @@ def match_descriptors(desc1, desc2, ratio=0.8, mutual=True, *, backend="gpu", de
     return matches, ratios[rows]
 
 
+def _check_k(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or not 1 <= k <= 8:
+        raise ValueError(f"k must be an integer in 1..8, got {k!r}")
+    return int(k)
+
+
+def knn_descriptors(desc1, desc2, k, *, backend="gpu", device=None):
+    """The exact ``k`` nearest neighbours of every row of ``desc1`` among the
+    rows of ``desc2``: ``match_descriptors``'s descriptors, distance and order
+    (squared Euclidean, an integer; on equal distances the lower index is
+    nearer), ``k`` in 1..8.
+
+    ``desc1`` is (n1, dim) and ``desc2`` (n2, dim), both uint8 (anything else
+    is a ValueError: ``quantize_descriptors`` converts float descriptors);
+    ``dim`` is a multiple of 32 in 32..512.  ``backend="gpu"`` runs the HIP
+    kernels (csrc/match_knn.hip: int8 matrix cores, exact), ``backend="host"``
+    the plain-loop definition on up to 16 threads, without a GPU; both give the
+    same bytes.
+
+    Returns ``(idx, dist)``, both (n1, k) uint32: row i holds the indices and
+    the distances of i's neighbours, nearest first; 0xFFFFFFFF in both from
+    position n2 on where ``desc2`` has fewer than ``k`` rows.  For ``k=2`` the
+    columns are the nearest and second-nearest neighbour ``match_descriptors``
+    works on.  ``matches_from_knn`` builds one-to-many matches from them."""
+    from . import _native as N
+
+    d1 = _as_descriptors(desc1, "desc1")
+    d2 = _as_descriptors(desc2, "desc2")
+    if d1.shape[1] != d2.shape[1]:
+        raise ValueError(f"desc1 and desc2 differ in dimension: {d1.shape[1]} and {d2.shape[1]}")
+    if d1.shape[1] % 32 or not 32 <= d1.shape[1] <= 512:
+        raise ValueError(f"the descriptor dimension must be a multiple of 32 in 32..512, got {d1.shape[1]}")
+    if d1.shape[0] == 0 or d2.shape[0] == 0:
+        raise ValueError("desc1 and desc2 need at least one row each")
+    if backend not in ("gpu", "host"):
+        raise ValueError(f"backend must be 'gpu' or 'host', got {backend!r}")
+    k = _check_k(k)
+    n1, dim = d1.shape
+    idx = np.empty((n1, k), dtype=np.uint32)
+    dist = np.empty((n1, k), dtype=np.uint32)
+    if backend == "host":
+        import os
+
+        threads = max(1, min(16, os.cpu_count() or 1))
+        N.check(N.lib.gcr_host_knn_descriptors(d1.ctypes.data, n1, d2.ctypes.data, d2.shape[0], dim, k, threads,
+                                               idx.ctypes.data, dist.ctypes.data))
+    else:
+        N.check(N.lib.gcr_knn_descriptors(N.context(device), d1.ctypes.data, n1, d2.ctypes.data, d2.shape[0], dim, k,
+                                          idx.ctypes.data, dist.ctypes.data, None))
+    return idx, dist
+
+
+def matches_from_knn(idx, dist, ratio=0.8, max_group=None):
+    """One-to-many matches from ``knn_descriptors``'s ``(idx, dist)``: the
+    ratio test generalised to a GROUP of equally good candidates.  Where a
+    descriptor repeats g times in the other image (facades, tiles, windows) the
+    first g neighbours are at about the same distance and the gap follows
+    them, so Lowe's test between the first and the second fails although the
+    true match is among the g.
+
+    For row i and a group size g = 1 .. min(k - 1, max_group) the gap holds
+    iff neighbour g exists (is not 0xFFFFFFFF) and ``float(dist[i, g - 1]) <
+    (ratio * ratio) * float(dist[i, g])`` in float64, ``match_descriptors``'s
+    comparison.  The row's group is the SMALLEST such g, and the row gives the
+    g matches (i, idx[i, 0]), ..., (i, idx[i, g - 1]); a row without a gap
+    gives none.  ``max_group=None`` allows every g up to k - 1.
+
+    Returns ``(matches, group, ratios)``: ``matches`` (M, 2) int64 rows (i, j)
+    sorted by i, then by rank; ``group`` (M,) int64, the size g of the group a
+    match belongs to; ``ratios`` (M,) float64, sqrt(dist[i, g - 1] / dist[i, g])
+    of its row.  For k = 2 this is ``match_descriptors(ratio=ratio,
+    mutual=False)``, rows and ratios.  ``1.0 / group`` is a valid
+    ``probabilities`` for the estimators' ``sampler=3`` (guided sampling, with
+    ``guided_stop=True``): one of g equally good candidates is the true one with
+    probability 1 / g at most."""
+    ix, ds = np.asarray(idx), np.asarray(dist)
+    if ix.ndim != 2 or ix.shape != ds.shape:
+        raise ValueError(f"idx and dist must have the same shape (n, k), got {ix.shape} and {ds.shape}")
+    if ix.dtype != np.uint32 or ds.dtype != np.uint32:
+        raise ValueError("idx and dist must be uint32 arrays (knn_descriptors' outputs)")
+    n, k = ix.shape
+    if not 1 <= k <= 8:
+        raise ValueError(f"k (the number of columns) must be in 1..8, got {k}")
+    if not (isinstance(ratio, (int, float, np.integer, np.floating)) and np.isfinite(ratio) and ratio > 0):
+        raise ValueError("ratio must be a finite number > 0")
+    if max_group is None:
+        gmax = k - 1
+    else:
+        if isinstance(max_group, bool) or not isinstance(max_group, (int, np.integer)) or max_group < 1:
+            raise ValueError(f"max_group must be None or an integer >= 1, got {max_group!r}")
+        gmax = min(k - 1, int(max_group))
+    rr = float(ratio) * float(ratio)
+    fd = ds.astype(np.float64)
+    grp = np.zeros(n, dtype=np.int64)                     # 0: no gap yet
+    for g in range(1, gmax + 1):
+        gap = (ix[:, g] != 0xFFFFFFFF) & (fd[:, g - 1] < rr * fd[:, g])
+        grp[(grp == 0) & gap] = g
+    rows = np.nonzero(grp)[0]
+    g = grp[rows]
+    i = np.repeat(rows, g)
+    rank = np.arange(len(i), dtype=np.int64) - np.repeat(np.cumsum(g) - g, g)
+    matches = np.stack([i.astype(np.int64), ix[i, rank].astype(np.int64)], axis=1).reshape(-1, 2)
+    row_ratio = np.sqrt(fd[rows, g - 1] / fd[rows, np.minimum(g, k - 1)])
+    return matches, np.repeat(g, g), np.repeat(row_ratio, g)
+
+
 def _positions(kp, name):
     """(N, 2) contiguous float64 (x, y) from keypoints (keypoints_to_array's columns 0 and 1) or an (N, 2) array."""
     if isinstance(kp, np.ndarray) and kp.ndim == 2 and kp.shape[1] == 2:
@@ -373,7 +484,7 @@ class DescriptorSet:
     the ratios and the row selection all run on the device, and one download
     of the matches ends the call: no descriptor crosses the bus again.  A set
     can stand on either side of a match, against itself too, any number of
-    times.
+    times.  ``a.knn(b, k)`` is ``knn_descriptors`` on the two resident sets.
 
     ``len(s)`` is the row count; ``s.dim``, ``s.has_keypoints``.  ``close()``
     frees the device memory (also at the end of a ``with`` block and on
@@ -503,6 +614,19 @@ class DescriptorSet:
         code = _GUIDED_KINDS[kind]
         return self._run(lambda mp, rp, cap, mo: N.lib.gcr_match_sets_guided(self._ctx, ha, hb, code, m.ctypes.data, T,
                                                                              opt, mp, rp, cap, mo, None))
+
+
+    def knn(self, other, k):
+        """``knn_descriptors(desc_self, desc_other, k)`` on the two resident
+        sets: the same ``(idx, dist)``, without the uploads."""
+        from . import _native as N
+
+        ha, hb = self._pair(other)
+        k = _check_k(k)
+        idx = np.empty((self._n, k), dtype=np.uint32)
+        dist = np.empty((self._n, k), dtype=np.uint32)
+        N.check(N.lib.gcr_knn_sets(self._ctx, ha, hb, k, idx.ctypes.data, dist.ctypes.data, None))
+        return idx, dist
 
 
 def match_pairs(sets, pairs, ratio=0.8, mutual=True):

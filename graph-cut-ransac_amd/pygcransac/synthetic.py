@@ -360,3 +360,56 @@ def problem_match(n: int = 1_000, shared: int = 400, seed: int = DEFAULT_SEED, d
     pairs = pairs[np.argsort(pairs[:, 0], kind="stable")]
     return (np.ascontiguousarray(kp1[p1]), np.ascontiguousarray(desc1[p1]), np.ascontiguousarray(kp2[p2]),
             np.ascontiguousarray(desc2[p2]), pairs, Hgt)
+
+
+def problem_match_repeated(n: int = 1_000, groups: int = 100, repeats: int = 3, seed: int = DEFAULT_SEED,
+                           desc_noise: float = 20.0, dim: int = 256):
+    """problem_match with REPEATED structure (facades, tiles, windows), for
+    knn_descriptors and matches_from_knn.  groups * repeats of each image's n
+    keypoints are shared scene points; the `repeats` scene points of a group
+    share ONE base descriptor (one uniform random byte vector per group) but
+    lie at independent positions: problem_hs's geometry under H_GT, as
+    problem_match's shared keypoints.  Each image adds its own Gaussian
+    descriptor noise of `desc_noise`, rounded and clipped to 0..255.  The other
+    keypoints of each image are independent; both images are permuted.  A
+    shared keypoint's nearest `repeats` neighbours are therefore the copies of
+    its group, at about equal distances, and the true one is any of them.
+    The distances inside a group scatter by about sqrt(2 / dim) of their mean
+    whatever the noise: at the default dim of 256 the smallest ratio of two of
+    them stays near 0.75, clear of the 0.8^2 = 0.64 of the usual ratio test
+    (at dim 128 it comes down to 0.62 in one row of 300), while the ratio to
+    the first neighbour outside the group is near 0.12.
+
+    Returns problem_match's tuple: (kp1 (n, 4), desc1 (n, dim) uint8, kp2,
+    desc2, pairs (groups * repeats, 2) int64 rows (i, j) of the same scene
+    point sorted by i, H_gt)."""
+    shared = groups * repeats
+    if groups < 0 or repeats < 1 or shared > n:
+        raise ValueError("need groups >= 0, repeats >= 1 and groups * repeats <= n")
+    c8, _, Hgt, _ = problem_hs(shared, 0.0, seed) if shared else (np.zeros((0, 8)), None, H_GT.copy(), None)
+    rng = np.random.default_rng([seed, 0x72657065])
+    rest = n - shared
+
+    def independent(k):
+        return np.column_stack([rng.uniform(0, IMG_W, k), rng.uniform(0, IMG_H, k),
+                                np.exp(rng.uniform(math.log(2.0), math.log(30.0), k)),
+                                np.degrees(rng.uniform(-math.pi, math.pi, k))])
+
+    kp1 = np.concatenate([np.column_stack([c8[:, 0], c8[:, 1], c8[:, 4], np.degrees(c8[:, 6])]), independent(rest)])
+    kp2 = np.concatenate([np.column_stack([c8[:, 2], c8[:, 3], c8[:, 5], np.degrees(c8[:, 7])]), independent(rest)])
+    # scene point s belongs to group s // repeats
+    base = np.repeat(rng.integers(0, 256, (groups, dim)).astype(np.float64), repeats, axis=0)
+
+    def noisy():
+        return np.clip(np.rint(base + rng.normal(0.0, desc_noise, base.shape)), 0, 255).astype(np.uint8)
+
+    desc1 = np.concatenate([noisy(), rng.integers(0, 256, (rest, dim), dtype=np.uint8)])
+    desc2 = np.concatenate([noisy(), rng.integers(0, 256, (rest, dim), dtype=np.uint8)])
+    p1, p2 = rng.permutation(n), rng.permutation(n)
+    inv1, inv2 = np.empty(n, np.int64), np.empty(n, np.int64)
+    inv1[p1] = np.arange(n)
+    inv2[p2] = np.arange(n)
+    pairs = np.stack([inv1[:shared], inv2[:shared]], axis=1)
+    pairs = pairs[np.argsort(pairs[:, 0], kind="stable")]
+    return (np.ascontiguousarray(kp1[p1]), np.ascontiguousarray(desc1[p1]), np.ascontiguousarray(kp2[p2]),
+            np.ascontiguousarray(desc2[p2]), pairs, Hgt)

@@ -853,6 +853,29 @@ int gcr_match_sets_guided(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_desc
 int gcr_match_set_pairs(gcr_ctx* ctx, const gcr_descriptors* const* sets, size_t nsets, const uint32_t* pairs,
                         size_t npairs, const gcr_match_options* opt, uint32_t* matches_out, double* ratios_out,
                         const size_t* offsets, size_t* m_out, double* ms_kernel_out);
+/* Exact k-nearest-neighbour search (csrc/match_knn.h is the definition,
+ * csrc/match_knn.hip the kernels): gcr_match_descriptors' arguments, ranges,
+ * distance and order, and 1 <= k <= 8.  idx_out / dist_out are n1 x k,
+ * row-major: row i holds the first k elements of the order (d(i, j), j), and
+ * 0xFFFFFFFF in both from position n2 on where n2 < k.  For k = 2 the two
+ * columns are gcr_match_descriptors' idx / idx2 and dist / dist2.  The device
+ * result equals gcr_host_knn_descriptors' bit for bit, under every
+ * GCR_MATCH_SPLIT.  A NULL buffer, a bad n1, n2, dim or k is GCR_EINVAL with a
+ * message naming the argument, before any GPU work.  ms_kernel_out may be
+ * NULL: HIP-event time of the kernels. */
+int gcr_knn_descriptors(gcr_ctx* ctx, const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim,
+                        uint32_t k, uint32_t* idx_out, uint32_t* dist_out, double* ms_kernel_out);
+/* host-only: the same by plain loops; `threads` (clamped to 1..64) splits the
+ * rows of d1 only and does not change the result */
+int gcr_host_knn_descriptors(const uint8_t* d1, size_t n1, const uint8_t* d2, size_t n2, uint32_t dim, uint32_t k,
+                             int threads, uint32_t* idx_out, uint32_t* dist_out);
+/* gcr_knn_descriptors on two resident sets (b may be a): the rows of `a`
+ * against `b`, idx_out / dist_out rows(a) x k.  The sets' buffers and norms
+ * and the context's matching workspace; one synchronisation and one download.
+ * ms_kernel_out may be NULL; else ONE double.  GCR_EINVAL naming the argument
+ * for a NULL argument, a bad k, a set of another context, sets of different dim. */
+int gcr_knn_sets(gcr_ctx* ctx, const gcr_descriptors* a, const gcr_descriptors* b, uint32_t k, uint32_t* idx_out,
+                 uint32_t* dist_out, double* ms_kernel_out);
 /* host-only: csrc/match_select.h's rule by plain loops on a search's results
  * (n rows).  back is NULL (no mutual check) or the reverse search's idx (nb
  * values).  guided selects the guided variant of the rule. */

@@ -37,6 +37,16 @@ a.match(b).  The legs of a group alternate call by call; medians of --calls
 after a warm-up, quartiles beside them; every set result is compared with the
 array function's byte for byte.
 
+With --knn only the k-nearest-neighbour legs run (gcr_knn_descriptors) on the
+uniform random descriptors: the kernels' time (HIP events) of the 2-NN matcher
+(k_match) and of the k-NN kernels at k = 2, 4 and 8, the legs alternating call
+by call in one process, under the planner's column split and each pinned split
+of --knn-splits; the whole-call times of the array entry and of the set entry
+(DescriptorSet.knn, both sets resident) with the set entry's kernel time; the
+ratio of every k-NN kernel time to k_match's of the same run; whether k = 2
+equals the matcher's arrays, the set entry the array entry and k = 8 the host
+twin.
+
 Prints one JSON line."""
 import argparse
 import ctypes as C
@@ -63,6 +73,8 @@ ap.add_argument("--threshold", type=float, default=3.0, help="guided: the bound 
 ap.add_argument("--sets", action="store_true", help="the resident descriptor sets' legs only")
 ap.add_argument("--pair-sets", type=int, default=16, help="sets: the number of sets of the match_pairs leg")
 ap.add_argument("--pair-calls", type=int, default=5, help="sets: timed repetitions of the match_pairs legs")
+ap.add_argument("--knn", action="store_true", help="the k-nearest-neighbour legs only")
+ap.add_argument("--knn-splits", default="0,1", help="knn: column splits to time (GCR_MATCH_SPLIT), 0 = the planner's")
 args = ap.parse_args()
 
 sys.path.insert(0, args.pkg)
@@ -314,6 +326,73 @@ def sets_mode():
     print(json.dumps(out))
 
 
+# ---- knn mode ------------------------------------------------------------------
+def knn_mode():
+    ks = (2, 4, 8)
+    ms = C.c_double()
+    two = [np.empty(n, dtype=np.uint32) for _ in range(4)]
+    res = {k: (np.empty((n, k), np.uint32), np.empty((n, k), np.uint32)) for k in ks}
+    sres = {k: (np.empty((n, k), np.uint32), np.empty((n, k), np.uint32)) for k in ks}
+    a, b = F.DescriptorSet(d1), F.DescriptorSet(d2)
+
+    def match_leg():
+        whole = gpu_call(two, ms)
+        return whole, ms.value
+
+    def knn_leg(k):
+        t0 = time.perf_counter()
+        N.check(N.lib.gcr_knn_descriptors(ctx, d1.ctypes.data, n, d2.ctypes.data, n, dim, k, res[k][0].ctypes.data,
+                                          res[k][1].ctypes.data, C.byref(ms)))
+        return (time.perf_counter() - t0) * 1e3, ms.value
+
+    def set_leg(k):
+        t0 = time.perf_counter()
+        N.check(N.lib.gcr_knn_sets(ctx, a._handle, b._handle, k, sres[k][0].ctypes.data, sres[k][1].ctypes.data,
+                                   C.byref(ms)))
+        return (time.perf_counter() - t0) * 1e3, ms.value
+
+    legs = {"k_match": match_leg}
+    for k in ks:
+        legs[f"knn_k{k}"] = lambda k=k: knn_leg(k)
+        legs[f"knn_set_k{k}"] = lambda k=k: set_leg(k)
+    g = {}
+    for s in [int(v) for v in args.knn_splits.split(",")]:
+        if s:
+            os.environ["GCR_MATCH_SPLIT"] = str(s)
+        else:
+            os.environ.pop("GCR_MATCH_SPLIT", None)
+        acc = {name: ([], []) for name in legs}
+        for c in range(-1, args.calls):                   # call -1 warms up; the legs alternate call by call
+            for name, fn in legs.items():
+                whole, kern = fn()
+                if c >= 0:
+                    acc[name][0].append(kern)
+                    acc[name][1].append(whole)
+        r = {name: {"kernel": quart(v[0]), "call": quart(v[1])} for name, v in acc.items()}
+        base = r["k_match"]["kernel"]["median_ms"]
+        for k in ks:
+            r[f"knn_k{k}"]["kernel_over_k_match"] = round(r[f"knn_k{k}"]["kernel"]["median_ms"] / base, 3)
+            r[f"knn_k{k}"]["mac_per_s"] = round(n * n * dim / (r[f"knn_k{k}"]["kernel"]["median_ms"] * 1e-3))
+        r["k2_equals_match_descriptors"] = bool(
+            np.array_equal(res[2][0][:, 0], two[0]) and np.array_equal(res[2][1][:, 0], two[1]) and
+            np.array_equal(res[2][0][:, 1], two[2]) and np.array_equal(res[2][1][:, 1], two[3]))
+        r["set_equals_array_entry"] = all(np.array_equal(res[k][q], sres[k][q]) for k in ks for q in (0, 1))
+        r["k4_is_a_prefix_of_k8"] = bool(np.array_equal(res[8][0][:, :4], res[4][0]) and
+                                         np.array_equal(res[8][1][:, :4], res[4][1]))
+        g[f"split{s}"] = r
+    os.environ.pop("GCR_MATCH_SPLIT", None)
+    hi, hd = np.empty((n, 8), np.uint32), np.empty((n, 8), np.uint32)
+    t0 = time.perf_counter()
+    N.check(N.lib.gcr_host_knn_descriptors(d1.ctypes.data, n, d2.ctypes.data, n, dim, 8, args.threads, hi.ctypes.data,
+                                           hd.ctypes.data))
+    g["host_twin_k8"] = {"threads": args.threads, "ms": round((time.perf_counter() - t0) * 1e3, 2),
+                         "equals_gpu_bitwise": bool(np.array_equal(hi, res[8][0]) and np.array_equal(hd, res[8][1]))}
+    a.close()
+    b.close()
+    out["knn"] = g
+    print(json.dumps(out))
+
+
 def workspace():
     w = (C.c_uint64 * 2)()
     N.check(N.lib.gcr_debug_match_workspace(ctx, w))
@@ -322,6 +401,9 @@ def workspace():
 
 if args.guided:
     guided_mode()
+    sys.exit(0)
+if args.knn:
+    knn_mode()
     sys.exit(0)
 if args.sets:
     sets_mode()
