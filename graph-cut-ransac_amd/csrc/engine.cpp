@@ -301,6 +301,7 @@ struct Workspace {
         DevBuf<uint8_t> inc, state;
         DevBuf<RectModel> models;
         DevBuf<uint32_t> ub0, ub1, map, cnt, n0, n1;
+        DevBuf<uint32_t> live;          // the group's live list (k_bound_live); its length is cnt's last word
         DevBuf<double> v0, v1, tot;
     } vbnd[3];
     hipEvent_t vb_flush = nullptr;
@@ -1853,23 +1854,32 @@ struct RectTraits {
         L.lstride = bnd::list_stride(n, L.cap1);
         const size_t ns = (size_t)gmax * n, nl = (size_t)gmax * L.lstride;
         b.inc.ensure(ns); b.state.ensure(ns); b.models.ensure(ns); b.ub0.ensure(ns); b.ub1.ensure(ns);
-        b.map.ensure(nl); b.cnt.ensure(2 * (size_t)gmax);
+        b.map.ensure(nl); b.cnt.ensure(2 * (size_t)gmax + 1); b.live.ensure(ns);
         b.n0.ensure(nl); b.n1.ensure(nl); b.v0.ensure(nl); b.v1.ensure(nl); b.tot.ensure(nl);
         L.ub0 = b.ub0.p; L.ub1 = b.ub1.p; L.state = b.state.p; L.map = b.map.p;
         L.count1 = b.cnt.p; L.count2 = b.cnt.p + gmax;
+        L.live = b.live.p; L.nlive = b.cnt.p + 2 * (size_t)gmax;
         sc = ScoreOut{b.n0.p, b.n1.p, b.v0.p, b.v1.p, b.tot.p};
         return L;
     }
+    // GCR_VERIFY_BOUND_LIVE=0 (read per call): k_bound walks every slot with a
+    // model, not only those that can be selected (A/B; the records are the same)
+    static bool bound_live_on() {
+        const char* e = getenv("GCR_VERIFY_BOUND_LIVE");
+        return !(e && e[0] == '0');
+    }
     // One launch group of `count` batches from slot s0 on stream s: generate,
-    // bound, seeds, their exact scores, contenders, theirs, selection -- all
-    // queued, the list sizes stay on the device.  rec[0 .. count): the records.
+    // live list, bound, seeds, their exact scores, contenders, theirs,
+    // selection -- all queued, the list sizes stay on the device.  `all`: the
+    // live list holds every slot with a model.  rec[0 .. count): the records.
     static hipError_t bound_group(gcr_problem* P, const double Tm[2], uint64_t seed, uint64_t s0, uint32_t n,
                                   const uint32_t m[2], uint32_t count, int set, const BoundLists& L,
-                                  const ScoreOut& sc, BatchRecord* rec, hipStream_t s) {
+                                  const ScoreOut& sc, bool all, BatchRecord* rec, hipStream_t s) {
         Workspace::BoundSet& b = P->w->vbnd[set];
         const uint32_t nh = count * n;
         hipError_t e = launch_generate(P->dp, seed, s0, nh, b.inc.p, b.models.p, s);
-        if (e == hipSuccess) e = launch_bound(P->dp, Tm, b.models.p, b.inc.p, nh, L.ub0, L.ub1, s);
+        if (e == hipSuccess) e = launch_bound_live(P->solver, all, b.inc.p, b.models.p, nh, L, s);
+        if (e == hipSuccess) e = launch_bound(P->dp, Tm, b.models.p, nh, L, s);
         if (e == hipSuccess) e = launch_bound_seeds(P->solver, b.inc.p, b.models.p, n, count, m, L, s);
         if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, 0, L, sc, s);
         if (e == hipSuccess) e = launch_bound_contenders(P->solver, sc, n, count, m, Tm, L, s);
@@ -2932,17 +2942,21 @@ public:
     // generated, scored and reduced to its first strict best on the device by
     // the fused scorer (launch_verify_fused); one host synchronisation at the end.
     // gcr_debug_verify_bound: the bound path's per-slot bounds (nb * nslots
-    // each) and per batch the slots it scored exactly, copied out group by group
+    // each) and per batch the slots it scored exactly, copied out group by
+    // group, with every slot that has a model on the live list (ub0 set); or
+    // gcr_debug_verify_bound_live: per batch the live list's slots in the
+    // default mode (walked set, ub0 / ub1 / scored null)
     struct BoundCapture {
         uint32_t* ub0;
         uint32_t* ub1;
         uint32_t* scored;
+        uint32_t* walked = nullptr;
         bool taken = false;                     // the call took the bound path
     };
     // The bound path (bound.h; Tr::bound_group): launch groups of up to G
     // batches, clipped like the fused path's (fm_groups.h), go round s_, the
     // aux stream and the side stream, each with its own buffer set.  A group
-    // is a chain of seven dependent launches, two of them the exact scorer
+    // is a chain of eight dependent launches, two of them the exact scorer
     // with a few workgroups and ~170 us each, so one stream alone leaves the
     // GPU idle most of the time: the other streams' bound kernels fill it.
     // Every group ends with its own selection; evs[0..1] bracket the whole
@@ -2960,6 +2974,7 @@ public:
             while (G > 1 && nb < 2 * G) G >>= 1;
             while (G > 1 && R % G != 0) --G;
             const uint32_t seeds = Tr::bound_seeds();
+            const bool all = cap != nullptr ? cap->walked == nullptr : !Tr::bound_live_on();
             ScoreOut sc[kStreams];
             BoundLists L[kStreams];
             for (int set = 0; set < kStreams; ++set) L[set] = Tr::bound_lists(P_, set, nslots, G, seeds, sc[set]);
@@ -2972,8 +2987,20 @@ public:
                 const int set = (int)(li % kStreams);
                 hipStream_t st = streams[set];
                 HIPC(Tr::bound_group(P_, Tm_, prm_.seed, slot0 + (uint64_t)b * nslots, nslots, m32, c, set, L[set],
-                                     sc[set], drecs + b, st));
-                if (cap != nullptr) {
+                                     sc[set], all, drecs + b, st));
+                if (cap != nullptr && cap->walked != nullptr) {
+                    // debug hook: the group's live list, counted per batch
+                    uint32_t nl = 0;
+                    HIPC(hipStreamSynchronize(st));
+                    HIPC(hipMemcpy(&nl, L[set].nlive, sizeof(uint32_t), hipMemcpyDeviceToHost));
+                    std::vector<uint32_t> live(std::min<size_t>(nl, (size_t)c * nslots));
+                    if (!live.empty())
+                        HIPC(hipMemcpy(live.data(), L[set].live, live.size() * sizeof(uint32_t), hipMemcpyDeviceToHost));
+                    for (uint32_t k = 0; k < c; ++k) cap->walked[b + k] = 0;
+                    for (uint32_t j : live)
+                        if (j / nslots < c) ++cap->walked[b + j / nslots];
+                    cap->taken = true;
+                } else if (cap != nullptr) {
                     // debug hook: this group's bounds and list sizes (the copies
                     // wait for the stream, so the set may be reused after them)
                     const size_t o = (size_t)b * nslots, ns = (size_t)c * nslots;
@@ -5261,6 +5288,25 @@ int gcr_debug_verify_bound(gcr_problem* prob, const gcr_params* params, uint64_t
         HIPC(hipSetDevice(prob->ctx->device));
         auto go = [&](auto&& r) {
             typename std::decay_t<decltype(r)>::BoundCapture cap{ub0_out, ub1_out, scored_out};
+            std::vector<gcr_batch_result> recs(nbatches);
+            r.verify_batches(slot0, nslots, nbatches, recs.data(), &cap);
+            if (!cap.taken) return set_err(GCR_EINVAL, "this call does not take the bound path");
+            return (int)GCR_OK;
+        };
+        return with_runner(prob, *params, go);
+    });
+}
+
+int gcr_debug_verify_bound_live(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
+                                uint32_t nbatches, uint32_t* walked_out) {
+    if (!prob || !walked_out) return set_err(GCR_EINVAL, "null problem or output");
+    if (prob->solver > GCR_SOLVER_SIFT22) return set_err(GCR_EINVAL, "the bound path scores rectification solvers");
+    if (int e = check_params(params, prob->solver)) return e;
+    if (nslots == 0 || nbatches == 0) return set_err(GCR_EINVAL, "nslots and nbatches must be > 0");
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(prob->ctx->device));
+        auto go = [&](auto&& r) {
+            typename std::decay_t<decltype(r)>::BoundCapture cap{nullptr, nullptr, nullptr, walked_out};
             std::vector<gcr_batch_result> recs(nbatches);
             r.verify_batches(slot0, nslots, nbatches, recs.data(), &cap);
             if (!cap.taken) return set_err(GCR_EINVAL, "this call does not take the bound path");

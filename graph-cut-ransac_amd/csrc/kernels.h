@@ -300,11 +300,18 @@ struct BoundLists {
     uint32_t* map = nullptr;
     uint32_t* count1 = nullptr;
     uint32_t* count2 = nullptr;
+    uint32_t* live = nullptr;       // the launch group's live list: the slots k_bound walks, in slot order
+    uint32_t* nlive = nullptr;      // its length, one word
     uint32_t seeds = 0, cap1 = 0, lstride = 0;
 };
-// k_bound<KIND>: ub0 / ub1 of nh slots (0 for a slot without a model)
-hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
-                        uint32_t nh, uint32_t* ub0, uint32_t* ub1, hipStream_t stream);
+// k_bound_live: L.live / L.nlive of the group's nh slots -- those with a model
+// and, for the 2-SIFT solver unless `all`, a valid one; ub0 = ub1 = 0 and state
+// kDead for every other slot
+hipError_t launch_bound_live(int solver, bool all, const uint8_t* inc, const RectModel* models, uint32_t nh,
+                             const BoundLists& L, hipStream_t stream);
+// k_bound<KIND>: ub0 / ub1 of the listed slots among the group's nh
+hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, uint32_t nh,
+                        const BoundLists& L, hipStream_t stream);
 // the seeds: about L.seeds live slots a batch with the largest ub0 + ub1, in slot order
 hipError_t launch_bound_seeds(int solver, const uint8_t* inc, const RectModel* models, uint32_t nslots,
                               uint32_t batches, const uint32_t m[2], const BoundLists& L, hipStream_t stream);

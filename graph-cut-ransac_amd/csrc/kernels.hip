@@ -4752,12 +4752,76 @@ __global__ __launch_bounds__(kSelectThreads) void k_select_wg(const WgBest* __re
 // other slot whose bound could still reach the seeds' best, the scorer scores
 // those, and k_bound_select takes the first strict best over both lists.
 //
-// k_bound: a wave owns kBoundHW consecutive slots and walks every feature, one
-// feature a lane and round, with exactly the scorer's constants (make_hyp,
-// rpb_setup) and tests (rpb_scale, rpb_orient).  The reject masks are compare
-// ballots, so the counts are scalar bit counts; nothing is queued or stored
-// until the two counts of each slot at the end.  LDS holds the wave's
-// constant records only.
+// k_bound_live: the live list of a launch group's nh slots -- in increasing
+// slot order the slots that k_bound walks: those with a model and, for the
+// 2-SIFT solver unless `all`, a valid one (k_bound_seeds' key is 0 for every
+// other slot, which is never a seed, a contender or the best).  Workgroup g
+// lists the slots [g, g + 1) * kLiveThreads; it counts the live slots below its
+// tile itself, so positions come from counts alone: no atomics, no workgroup
+// waits for another.  Every slot off the list gets ub0 = ub1 = 0 and state
+// kDead here, every listed slot its bounds from k_bound, so the reused buffers
+// keep nothing of an earlier group.  *count: the list's length.
+constexpr int kLiveThreads = 1024;
+
+__global__ __launch_bounds__(kLiveThreads) void k_bound_live(int solver, int all, const uint8_t* __restrict__ inc,
+                                                             const RectModel* __restrict__ models, uint32_t nh,
+                                                             uint32_t* __restrict__ list, uint32_t* __restrict__ count,
+                                                             uint32_t* __restrict__ ub0, uint32_t* __restrict__ ub1,
+                                                             uint8_t* __restrict__ state) {
+    constexpr uint32_t kWaves = kLiveThreads / 64;
+    __shared__ uint32_t wpre[kWaves], wsum[kWaves];
+    const uint32_t t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const bool rule = solver == GCR_SOLVER_SIFT22 && !all;
+    auto live = [&](uint32_t j) -> bool { return inc[j] <= 101 && (!rule || valid_model_sift22(models[j])); };
+    const uint32_t j0 = blockIdx.x * kLiveThreads;
+    // the tiles below: a slot's model is loaded whatever its inc says, so the
+    // loads of the unrolled rounds are all in flight together
+    uint32_t pre = 0;
+    if (rule) {
+#pragma unroll 8
+        for (uint32_t j = t; j < j0; j += kLiveThreads) {
+            const bool has = inc[j] <= 101, ok = valid_model_sift22(models[j]);
+            pre += (has & ok) ? 1u : 0u;
+        }
+    } else {
+#pragma unroll 8
+        for (uint32_t j = t; j < j0; j += kLiveThreads) pre += inc[j] <= 101 ? 1u : 0u;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) pre += __shfl_xor(pre, d);
+    const uint32_t j = j0 + t;
+    const bool k = j < nh && live(j);
+    const uint64_t m = __builtin_amdgcn_ballot_w64(k);
+    const uint32_t below = __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    if (lane == 0) {
+        wpre[w] = pre;
+        wsum[w] = (uint32_t)__builtin_popcountll(m);
+    }
+    __syncthreads();
+    uint32_t base = 0, wb = 0, tot = 0;
+#pragma unroll
+    for (uint32_t x = 0; x < kWaves; ++x) {
+        const uint32_t sv = wsum[x];
+        base += wpre[x];
+        wb += x < w ? sv : 0u;
+        tot += sv;
+    }
+    if (k) list[base + wb + below] = j;                  // < nh: one position per live slot
+    else if (j < nh) {
+        ub0[j] = 0u;
+        ub1[j] = 0u;
+        state[j] = bnd::kDead;
+    }
+    if (blockIdx.x == gridDim.x - 1 && t == 0) *count = base + tot;
+}
+
+// k_bound: a wave owns kBoundHW consecutive entries of the live list and walks
+// every feature, one feature a lane and round, with exactly the scorer's
+// constants (make_hyp, rpb_setup) and tests (rpb_scale, rpb_orient).  The
+// reject masks are compare ballots, so the counts are scalar bit counts;
+// nothing is queued or stored until the two counts of each slot at the end.
+// LDS holds the wave's constant records only.  The grid covers the list's
+// capacity nh; the waves past *count leave after the barrier.
 constexpr int kBoundThreads = 256;
 constexpr int kBoundWaves = kBoundThreads / 64;
 constexpr int kBoundHW = 16;
@@ -4765,23 +4829,27 @@ constexpr int kBoundHW = 16;
 template <int KIND>
 __global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double band0, double tan_tau1,
                                                          const RectModel* __restrict__ models,
-                                                         const uint8_t* __restrict__ inc, uint32_t nh,
+                                                         const uint32_t* __restrict__ list,
+                                                         const uint32_t* __restrict__ count, uint32_t nh,
                                                          uint32_t* __restrict__ ub0, uint32_t* __restrict__ ub1) {
     static_assert(KIND <= 2 && kBoundHW % 2 == 0 && kBoundHW <= 64, "rectification kinds, whole pairs");
     __shared__ RPairBand pbs[kBoundWaves][kBoundHW / 2];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const uint32_t h0 = (blockIdx.x * kBoundWaves + (uint32_t)wave) * kBoundHW;
+    const uint32_t nl = min(*count, nh);
     bool v = false;
+    uint32_t hg = 0;
     if (lane < kBoundHW) {
-        const uint32_t hg = h0 + lane;
-        v = hg < nh && inc[hg] <= 101;
+        v = h0 + lane < nl;
+        hg = v ? list[h0 + lane] : 0u;
+        v = v && hg < nh;
         const RectModel m = v ? models[hg] : default_model();
         const HypConst q = make_hyp<KIND>(m, band0);
         rpb_setup(pbs[wave], lane, q, p.cls[0].amax, p.cls[1].amax, tan_tau1, KIND == 2, v);
     }
     __syncthreads();
-    if (h0 >= nh) return;
+    if (h0 >= nl) return;
     const RPairBand* pb = pbs[wave];
     uint32_t cnt0[kBoundHW], cnt1[kBoundHW];
 #pragma unroll
@@ -4847,9 +4915,9 @@ __global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double ba
         my0 = lane == q ? cnt0[q] : my0;
         my1 = lane == q ? cnt1[q] : my1;
     });
-    if (lane < kBoundHW && h0 + lane < nh) {
-        ub0[h0 + lane] = v ? my0 : 0u;
-        ub1[h0 + lane] = v ? my1 : 0u;
+    if (v) {
+        ub0[hg] = my0;
+        ub1[hg] = my1;
     }
 }
 
@@ -5509,17 +5577,30 @@ hipError_t launch_select_batches(const WgBest* wg, size_t wg_stride, const RectM
 }
 
 // ---- the bound path's launches (kernels.h) ----
-hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
-                        uint32_t nh, uint32_t* ub0, uint32_t* ub1, hipStream_t stream) {
+hipError_t launch_bound_live(int solver, bool all, const uint8_t* inc, const RectModel* models, uint32_t nh,
+                             const BoundLists& L, hipStream_t stream) {
     if (nh == 0) return hipSuccess;
-    if (p.kind > GCR_SOLVER_SIFT22) return hipErrorInvalidValue;
+    if (solver > GCR_SOLVER_SIFT22 || L.live == nullptr || L.nlive == nullptr) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(k_bound_live, dim3((nh + kLiveThreads - 1) / kLiveThreads), dim3(kLiveThreads), 0, stream, solver,
+                       all ? 1 : 0, inc, models, nh, L.live, L.nlive, L.ub0, L.ub1, L.state);
+    return hipGetLastError();
+}
+
+hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, uint32_t nh,
+                        const BoundLists& L, hipStream_t stream) {
+    if (nh == 0) return hipSuccess;
+    if (p.kind > GCR_SOLVER_SIFT22 || L.live == nullptr || L.nlive == nullptr) return hipErrorInvalidValue;
+    const uint32_t* list = L.live;
+    const uint32_t* count = L.nlive;
+    uint32_t* ub0 = L.ub0;
+    uint32_t* ub1 = L.ub1;
     double band0, tan_tau1;
     band_consts(T, band0, tan_tau1);
     const dim3 grid((nh + kBoundWaves * kBoundHW - 1) / (kBoundWaves * kBoundHW)), block(kBoundThreads);
     switch (p.kind) {
-        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL(k_bound<0>, grid, block, 0, stream, p, band0, tan_tau1, models, inc, nh, ub0, ub1); break;
-        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL(k_bound<1>, grid, block, 0, stream, p, band0, tan_tau1, models, inc, nh, ub0, ub1); break;
-        default: hipLaunchKernelGGL(k_bound<2>, grid, block, 0, stream, p, band0, tan_tau1, models, inc, nh, ub0, ub1); break;
+        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL(k_bound<0>, grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL(k_bound<1>, grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
+        default: hipLaunchKernelGGL(k_bound<2>, grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
     }
     return hipGetLastError();
 }

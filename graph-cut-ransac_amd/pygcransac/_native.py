@@ -184,6 +184,7 @@ def _load():
     L.gcr_debug_score.argtypes = [vp, C.POINTER(Params), C.POINTER(RectModel), C.c_uint32, u32p, u32p, dp, dp, dp]
     L.gcr_debug_verify_slots.argtypes = [vp, C.POINTER(Params), C.c_uint64, C.c_uint32, u8p, u32p, u32p, dp, dp, dp]
     L.gcr_debug_verify_bound.argtypes = [vp, C.POINTER(Params), C.c_uint64, C.c_uint32, C.c_uint32, u32p, u32p, u32p]
+    L.gcr_debug_verify_bound_live.argtypes = [vp, C.POINTER(Params), C.c_uint64, C.c_uint32, C.c_uint32, u32p]
     L.gcr_debug_score_less.argtypes = [vp, C.POINTER(Params), C.POINTER(RectModel), C.POINTER(RectModel)]
     L.gcr_debug_exchange_log.argtypes = [C.POINTER(C.c_uint64), C.c_size_t]
     L.gcr_debug_exchange_log.restype = C.c_size_t

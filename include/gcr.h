@@ -475,10 +475,17 @@ int gcr_debug_verify_slots(gcr_problem* prob, const gcr_params* params, uint64_t
  * features that pass the conservative pre-band -- ub0_out / ub1_out,
  * nbatches * nslots entries each, upper bounds of the slot's inlier counts, 0
  * for a slot without a model -- and per batch in scored_out[nbatches] how many
- * slots were scored exactly.  GCR_EINVAL when the call would not take the
- * bound path. */
+ * slots were scored exactly.  The hook bounds every slot with a model, as
+ * GCR_VERIFY_BOUND_LIVE=0 does; the records and scored_out do not depend on
+ * that.  GCR_EINVAL when the call would not take the bound path. */
 int gcr_debug_verify_bound(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
                            uint32_t nbatches, uint32_t* ub0_out, uint32_t* ub1_out, uint32_t* scored_out);
+/* The same call in the default mode, whatever GCR_VERIFY_BOUND_LIVE says:
+ * walked_out[nbatches], per batch the slots on the live list, i.e. those whose
+ * bounds k_bound counted -- the slots with a model and, for the 2-SIFT solver,
+ * a valid one.  GCR_EINVAL as above. */
+int gcr_debug_verify_bound_live(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
+                                uint32_t nbatches, uint32_t* walked_out);
 /* The run loop's score comparison `score(a) < score(b)` (GCRANSAC.h:440) as
  * gcr_problem_run takes it: both models scored by the GPU small scorer (value
  * scores), compared directly when they are further apart than their proven
