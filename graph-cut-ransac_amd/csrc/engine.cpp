@@ -303,6 +303,8 @@ struct Workspace {
         DevBuf<uint32_t> ub0, ub1, map, cnt, n0, n1;
         DevBuf<uint32_t> live;          // the group's live list (k_bound_live); its length is cnt's last word
         DevBuf<double> v0, v1, tot;
+        DevBuf<double> lvals;           // the list scorer's scratch (launch_list_scores): a group's batches x
+        DevBuf<uint32_t> lmeta;         // kListCap models, allocated by the first call that scores lists with it
     } vbnd[3];
     hipEvent_t vb_flush = nullptr;
     hipEvent_t vb_aux = nullptr;       // verify_batches: the aux scoring stream's last batch of a ring
@@ -1846,7 +1848,20 @@ struct RectTraits {
         const int v = e ? atoi(e) : 0;
         return v >= 1 ? (uint32_t)std::min(v, 4096) : 64u;
     }
-    static BoundLists bound_lists(gcr_problem* P, int set, uint32_t n, uint32_t gmax, uint32_t seeds, ScoreOut& sc) {
+    // GCR_VERIFY_BOUND_LISTCAP (read per call): the entries of a batch's list
+    // the list scorer takes, 0 .. kListCap rounded down to a multiple of 4,
+    // default kListCap; the batch scorer takes the rest, with 0 every entry (A/B;
+    // the records are the same).  Problems with more pairs than the list
+    // scorer's fold holds go to the batch scorer whole.
+    static uint32_t bound_listcap(gcr_problem* P) {
+        const size_t pairs = small_score_pairs(P->dp);
+        if (pairs == 0 || pairs > kSplitMaxPairs) return 0;
+        const char* e = getenv("GCR_VERIFY_BOUND_LISTCAP");
+        const int v = e ? atoi(e) : (int)kListCap;
+        return (uint32_t)std::min(std::max(v, 0), (int)kListCap) & ~3u;
+    }
+    static BoundLists bound_lists(gcr_problem* P, int set, uint32_t n, uint32_t gmax, uint32_t seeds, uint32_t lcap,
+                                  ScoreOut& sc) {
         Workspace::BoundSet& b = P->w->vbnd[set];
         BoundLists L;
         L.seeds = seeds;
@@ -1854,11 +1869,18 @@ struct RectTraits {
         L.lstride = bnd::list_stride(n, L.cap1);
         const size_t ns = (size_t)gmax * n, nl = (size_t)gmax * L.lstride;
         b.inc.ensure(ns); b.state.ensure(ns); b.models.ensure(ns); b.ub0.ensure(ns); b.ub1.ensure(ns);
-        b.map.ensure(nl); b.cnt.ensure(2 * (size_t)gmax + 1); b.live.ensure(ns);
+        b.map.ensure(nl); b.cnt.ensure(4 * (size_t)gmax + 1); b.live.ensure(ns);
         b.n0.ensure(nl); b.n1.ensure(nl); b.v0.ensure(nl); b.v1.ensure(nl); b.tot.ensure(nl);
         L.ub0 = b.ub0.p; L.ub1 = b.ub1.p; L.state = b.state.p; L.map = b.map.p;
         L.count1 = b.cnt.p; L.count2 = b.cnt.p + gmax;
         L.live = b.live.p; L.nlive = b.cnt.p + 2 * (size_t)gmax;
+        L.over1 = L.nlive + 1; L.over2 = L.over1 + gmax;
+        L.lcap = lcap;
+        if (lcap > 0) {
+            const size_t pairs = small_score_pairs(P->dp), nm = (size_t)gmax * kListCap;
+            b.lvals.ensure(nm * pairs); b.lmeta.ensure(nm * (pairs / 64));
+            L.scratch = SmallScratch{b.lvals.p, b.lmeta.p, (uint32_t)nm, nullptr, nullptr};
+        }
         sc = ScoreOut{b.n0.p, b.n1.p, b.v0.p, b.v1.p, b.tot.p};
         return L;
     }
@@ -1870,7 +1892,9 @@ struct RectTraits {
     }
     // One launch group of `count` batches from slot s0 on stream s: generate,
     // live list, bound, seeds, their exact scores, contenders, theirs,
-    // selection -- all queued, the list sizes stay on the device.  `all`: the
+    // selection -- all queued, the list sizes stay on the device.  A list's
+    // scores: launch_list_scores and, where the list can be longer than L.lcap,
+    // launch_score_lists for the entries past it.  `all`: the
     // live list holds every slot with a model.  rec[0 .. count): the records.
     static hipError_t bound_group(gcr_problem* P, const double Tm[2], uint64_t seed, uint64_t s0, uint32_t n,
                                   const uint32_t m[2], uint32_t count, int set, const BoundLists& L,
@@ -1881,9 +1905,12 @@ struct RectTraits {
         if (e == hipSuccess) e = launch_bound_live(P->solver, all, b.inc.p, b.models.p, nh, L, s);
         if (e == hipSuccess) e = launch_bound(P->dp, Tm, b.models.p, nh, L, s);
         if (e == hipSuccess) e = launch_bound_seeds(P->solver, b.inc.p, b.models.p, n, count, m, L, s);
-        if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, 0, L, sc, s);
-        if (e == hipSuccess) e = launch_bound_contenders(P->solver, sc, n, count, m, Tm, L, s);
-        if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, 1, L, sc, s);
+        for (int list = 0; list < 2; ++list) {
+            if (list == 1 && e == hipSuccess) e = launch_bound_contenders(P->solver, sc, n, count, m, Tm, L, s);
+            // the first L.lcap entries by the list scorer, the rest by the batch scorer
+            if (L.lcap > 0 && e == hipSuccess) e = launch_list_scores(P->dp, Tm, b.models.p, n, count, list, L, sc, s);
+            if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, list, L, sc, s, L.lcap);
+        }
         if (e == hipSuccess) e = launch_bound_select(P->solver, sc, b.inc.p, b.models.p, n, s0, count, m, Tm, L, rec, s);
         return e;
     }
@@ -2956,9 +2983,9 @@ public:
     // The bound path (bound.h; Tr::bound_group): launch groups of up to G
     // batches, clipped like the fused path's (fm_groups.h), go round s_, the
     // aux stream and the side stream, each with its own buffer set.  A group
-    // is a chain of eight dependent launches, two of them the exact scorer
-    // with a few workgroups and ~170 us each, so one stream alone leaves the
-    // GPU idle most of the time: the other streams' bound kernels fill it.
+    // is a chain of dependent launches (eleven; eight when the batch scorer
+    // scores whole lists, Tr::bound_listcap), so one stream alone leaves the
+    // GPU idle most of the time: the other streams' kernels fill it.
     // Every group ends with its own selection; evs[0..1] bracket the whole
     // call on s_.
     void verify_batches_bound(uint64_t slot0, uint32_t nslots, uint32_t nb, const uint32_t m32[2], BatchRecord* drecs,
@@ -2977,7 +3004,8 @@ public:
             const bool all = cap != nullptr ? cap->walked == nullptr : !Tr::bound_live_on();
             ScoreOut sc[kStreams];
             BoundLists L[kStreams];
-            for (int set = 0; set < kStreams; ++set) L[set] = Tr::bound_lists(P_, set, nslots, G, seeds, sc[set]);
+            const uint32_t lcap = Tr::bound_listcap(P_);
+            for (int set = 0; set < kStreams; ++set) L[set] = Tr::bound_lists(P_, set, nslots, G, seeds, lcap, sc[set]);
             HIPC(hipEventRecord(w->evs[0], s_));
             HIPC(hipEventRecord(w->vb_start, s_));
             for (int k = 1; k < kStreams; ++k) HIPC(hipStreamWaitEvent(streams[k], w->vb_start, 0));

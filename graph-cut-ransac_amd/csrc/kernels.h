@@ -303,7 +303,15 @@ struct BoundLists {
     uint32_t* live = nullptr;       // the launch group's live list: the slots k_bound walks, in slot order
     uint32_t* nlive = nullptr;      // its length, one word
     uint32_t seeds = 0, cap1 = 0, lstride = 0;
+    // the list scorer (launch_list_scores): it scores the first lcap entries of
+    // a list, the batch scorer the over1 / over2 = count - min(count, lcap)
+    // entries after them (one word a batch, written with the counts)
+    uint32_t lcap = 0;              // 0: the batch scorer scores whole lists
+    uint32_t* over1 = nullptr;
+    uint32_t* over2 = nullptr;
+    SmallScratch scratch;           // the buffer set's: batches x lcap models (psum / arrive unused)
 };
+constexpr uint32_t kListCap = 128;  // list entries a batch the list scorer takes at most (a multiple of 4)
 // k_bound_live: L.live / L.nlive of the group's nh slots -- those with a model
 // and, for the 2-SIFT solver unless `all`, a valid one; ub0 = ub1 = 0 and state
 // kDead for every other slot
@@ -316,9 +324,18 @@ hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel*
 hipError_t launch_bound_seeds(int solver, const uint8_t* inc, const RectModel* models, uint32_t nslots,
                               uint32_t batches, const uint32_t m[2], const BoundLists& L, hipStream_t stream);
 // exact scores (k_score_split<KIND, 4, 960>, the counts read on the device) of
-// every batch's seeds (list 0) or contenders (list 1) at their list positions
+// every batch's seeds (list 0) or contenders (list 1) at their list positions;
+// skip = L.lcap: only of the entries from position lcap on (L.over1 / L.over2
+// of them), no launch when the list cannot hold more than lcap
 hipError_t launch_score_lists(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
                               uint32_t nslots, uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
+                              hipStream_t stream, uint32_t skip = 0);
+// the same sums, bit for bit, of the first min(count, L.lcap) entries of every
+// batch's list by the split scorer (k_list_resid + k_list_fold: one thread a
+// (model, feature) pair, then one workgroup a model folds its inlier values in
+// feature order); at most kSplitMaxPairs pairs, L.scratch for batches x lcap models
+hipError_t launch_list_scores(const DevProblem& p, const double T[2], const RectModel* models, uint32_t nslots,
+                              uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
                               hipStream_t stream);
 // the contenders: live slots outside the seeds with ub0 + ub1 + 1 > the seeds' best finished score
 hipError_t launch_bound_contenders(int solver, const ScoreOut& sc, uint32_t nslots, uint32_t batches,

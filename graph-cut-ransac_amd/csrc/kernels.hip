@@ -3481,6 +3481,83 @@ __global__ __launch_bounds__(kLoThreads) void k_lo_fold(DevProblem p, uint32_t p
     lo_fold_model<KIND>(p, src + blockIdx.x, pad0, nchunks, out, slot + blockIdx.x);
 }
 
+// The split scorer over the bound path's lists (launch_list_scores): entry j
+// of batch b's list -- j < min(count[b], cap) -- is model hmap[b lstride + j]
+// of the batch's nslots models, its chunks go to scratch model b cap + j of
+// p.lo, its sums to position b lstride + j of `out`.  hmap and out point at
+// the list's first entry of batch 0.
+struct ListArgs {
+    const uint32_t* hmap;
+    const uint32_t* count;      // one word a batch, read here: the host never sees the list sizes
+    uint32_t cap, lstride, nslots;
+};
+// k_lo_resid's work: grid (chunk groups, entries, batches), one chunk a wave;
+// a workgroup row past the list's count returns at once, so the work follows
+// the count.  kStride (A/B builds, see launch_list_scores): a grid of fewer
+// rows than entries or fewer chunk groups than chunks strides over them.
+template <int KIND, bool kStride>
+__global__ __launch_bounds__(kLrThreads) void k_list_resid(DevProblem p,
+                                                          const typename ModelOf<KIND>::type* __restrict__ models,
+                                                          double T0, double T1, uint32_t pad0, uint32_t nchunks,
+                                                          FlagBand fbm, ListArgs la) {
+    const uint32_t b = blockIdx.z;
+    const uint32_t cnt = min(la.count[b], la.cap);
+    if (blockIdx.y >= cnt) return;                            // whole workgroup, before any barrier
+    const int lane = threadIdx.x & 63;
+    const uint32_t c0 = blockIdx.x * (kLrThreads / 64) + (threadIdx.x >> 6);
+    const ListBits lb{{0.0, 0.0}, 0, 0.0, nullptr, nullptr};
+    // the first chunk's features before the model and its value constants, as in k_lo_resid
+    int cls;
+    uint32_t fi, held = c0 < nchunks ? c0 : 0u;
+    double x, y, f2, f3;
+    lo_pair_features<KIND>(p, held, lane, pad0, cls, fi, x, y, f2, f3);
+    __shared__ typename ModelOf<KIND>::type m_sh;
+    __shared__ ValueConst vc_sh;
+    models += (size_t)b * la.nslots;
+    const uint32_t* hmap = la.hmap + (size_t)b * la.lstride;
+    if constexpr (!kStride) {
+        const uint32_t j = blockIdx.y;
+        if (threadIdx.x == 0) {
+            m_sh = models[hmap[j]];
+            vc_sh = value_const(m_sh, KIND == 1, KIND == 2);
+        }
+        __syncthreads();
+        if (c0 >= nchunks) return;                            // wave-uniform, after the barrier
+        lo_resid_chunk<KIND>(p, m_sh, vc_sh, nullptr, b * la.cap + j, c0, lane, T0, T1, pad0, nchunks, lb, fbm, fbm, x,
+                             y, f2, f3, cls, fi);
+    } else {
+        const uint32_t cstep = gridDim.x * (kLrThreads / 64);
+#pragma unroll 1
+        for (uint32_t j = blockIdx.y; j < cnt; j += gridDim.y) {  // workgroup-uniform
+            if (j != blockIdx.y) __syncthreads();             // the last entry's model is read no more
+            if (threadIdx.x == 0) {
+                m_sh = models[hmap[j]];
+                vc_sh = value_const(m_sh, KIND == 1, KIND == 2);
+            }
+            __syncthreads();
+#pragma unroll 1
+            for (uint32_t c = c0; c < nchunks; c += cstep) {  // wave-uniform, no barrier inside
+                if (c != held) {
+                    lo_pair_features<KIND>(p, c, lane, pad0, cls, fi, x, y, f2, f3);
+                    held = c;
+                }
+                lo_resid_chunk<KIND>(p, m_sh, vc_sh, nullptr, b * la.cap + j, c, lane, T0, T1, pad0, nchunks, lb, fbm,
+                                     fbm, x, y, f2, f3, cls, fi);
+            }
+        }
+    }
+}
+
+// k_lo_fold's work: grid (entries, batches), one workgroup an entry (a fixed
+// grid whose rows stride over the entries was measured slower, MEASUREMENTS.md §2)
+template <int KIND>
+__global__ __launch_bounds__(kLoThreads) void k_list_fold(DevProblem p, uint32_t pad0, uint32_t nchunks, ScoreOut out,
+                                                         ListArgs la) {
+    const uint32_t b = blockIdx.y, j = blockIdx.x;
+    if (j >= min(la.count[b], la.cap)) return;                // whole workgroup, before any barrier
+    lo_fold_model<KIND>(p, b * la.cap + j, pad0, nchunks, out, b * la.lstride + j);
+}
+
 // The approximate scores of k_lo_resid's models (blockIdx.x) from its chunk
 // partial sums (p.lo.psum): exact counts and flag counts, class sums in a
 // fixed tree order instead of the reference's sequential one.  The host
@@ -4966,7 +5043,8 @@ __global__ __launch_bounds__(kSelectThreads) void k_bound_seeds(int solver, cons
                                                                 uint32_t m0, uint32_t m1, uint32_t seeds,
                                                                 uint32_t cap1, uint32_t lstride,
                                                                 uint32_t* __restrict__ map,
-                                                                uint32_t* __restrict__ count1,
+                                                                uint32_t* __restrict__ count1, uint32_t lcap,
+                                                                uint32_t* __restrict__ over1,
                                                                 uint8_t* __restrict__ state) {
     const size_t o = (size_t)blockIdx.x * n;
     inc += o; models += o; ub0 += o; ub1 += o; state += o;
@@ -5010,7 +5088,10 @@ __global__ __launch_bounds__(kSelectThreads) void k_bound_seeds(int solver, cons
         return k != 0 && bin(k) >= cut;
     });
     const uint32_t c1 = min(kept, cap1);
-    if (t == 0) count1[blockIdx.x] = c1;
+    if (t == 0) {
+        count1[blockIdx.x] = c1;
+        over1[blockIdx.x] = c1 - min(c1, lcap);              // entries past the list scorer's (launch_list_scores)
+    }
     __syncthreads();
     // the slots' states: the first c1 kept slots are the seeds (map is in slot
     // order, so a kept slot is a seed iff it is at most the last listed one)
@@ -5034,7 +5115,8 @@ __global__ __launch_bounds__(kSelectThreads) void k_bound_contenders(int solver,
                                                                      uint32_t cap1, uint32_t lstride,
                                                                      uint32_t* __restrict__ map,
                                                                      const uint32_t* __restrict__ count1,
-                                                                     uint32_t* __restrict__ count2) {
+                                                                     uint32_t* __restrict__ count2, uint32_t lcap,
+                                                                     uint32_t* __restrict__ over2) {
     const size_t o = (size_t)blockIdx.x * n, lo = (size_t)blockIdx.x * lstride;
     ub0 += o; ub1 += o; state += o;
     map += lo;
@@ -5066,7 +5148,10 @@ __global__ __launch_bounds__(kSelectThreads) void k_bound_contenders(int solver,
         const uint32_t b = ub0[j] + (K == 2 ? ub1[j] : 0u);
         return (double)b + 1.0 > S;
     });
-    if (t == 0) count2[blockIdx.x] = kept;
+    if (t == 0) {
+        count2[blockIdx.x] = kept;
+        over2[blockIdx.x] = kept - min(kept, lcap);
+    }
 }
 
 // The record of batch blockIdx.x: first strict best over both lists -- the
@@ -5610,21 +5695,22 @@ hipError_t launch_bound_seeds(int solver, const uint8_t* inc, const RectModel* m
     if (batches == 0 || nslots == 0) return hipSuccess;
     if (L.lstride < bnd::list_stride(nslots, L.cap1) || L.seeds == 0) return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_bound_seeds, dim3(batches), dim3(kSelectThreads), 0, stream, solver, inc, models, L.ub0, L.ub1,
-                       nslots, m[0], m[1], L.seeds, L.cap1, L.lstride, L.map, L.count1, L.state);
+                       nslots, m[0], m[1], L.seeds, L.cap1, L.lstride, L.map, L.count1, L.lcap, L.over1, L.state);
     return hipGetLastError();
 }
 
 hipError_t launch_score_lists(const DevProblem& p, const double T[2], const RectModel* models, const uint8_t* inc,
                               uint32_t nslots, uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
-                              hipStream_t stream) {
+                              hipStream_t stream, uint32_t skip) {
     if (batches == 0 || nslots == 0) return hipSuccess;
-    if (p.kind > GCR_SOLVER_SIFT22) return hipErrorInvalidValue;
+    if (p.kind > GCR_SOLVER_SIFT22 || (skip != 0 && skip != L.lcap) || skip % 4 != 0) return hipErrorInvalidValue;
     constexpr int H = 4, R = 960;
-    const uint32_t off = list ? L.cap1 : 0u, cap = list ? nslots : L.cap1;
+    if ((list ? nslots : L.cap1) <= skip) return hipSuccess;     // the list cannot be longer than `skip`
+    const uint32_t off = (list ? L.cap1 : 0u) + skip, cap = (list ? nslots : L.cap1) - skip;
     ScoreOut o{out.n0 + off, out.n1 + off, out.v0 + off, out.v1 + off, out.tot + off};
     GenArgs g{};
     g.hmap = L.map + off;
-    g.hcount = list ? L.count2 : L.count1;
+    g.hcount = skip ? (list ? L.over2 : L.over1) : (list ? L.count2 : L.count1);
     g.slot_stride = L.lstride;
     g.models_stride = nslots;
     const dim3 grid((cap + H - 1) / H, batches), block(kSplitThreads);
@@ -5638,11 +5724,61 @@ hipError_t launch_score_lists(const DevProblem& p, const double T[2], const Rect
     return hipGetLastError();
 }
 
+// GCR_LIST_ROWS / GCR_LIST_CPW (compile time, `make variant`): the residual
+// launch's grid.  Default: one grid row per list entry and one chunk per wave,
+// rows past a list's count return at once.  GCR_LIST_ROWS = r > 0: r rows a
+// batch stride over the entries; GCR_LIST_CPW = c: each wave strides over c
+// chunks.  Measured on MI355X (MEASUREMENTS.md §1): the default form wins.
+#ifndef GCR_LIST_ROWS
+#define GCR_LIST_ROWS 0
+#endif
+#ifndef GCR_LIST_CPW
+#define GCR_LIST_CPW 1
+#endif
+
+hipError_t launch_list_scores(const DevProblem& p, const double T[2], const RectModel* models, uint32_t nslots,
+                              uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
+                              hipStream_t stream) {
+    if (batches == 0 || nslots == 0) return hipSuccess;
+    const uint32_t ntot = (uint32_t)small_score_pairs(p);
+    if (p.kind > GCR_SOLVER_SIFT22 || ntot == 0 || ntot > kSplitMaxPairs || L.lcap == 0 || L.lcap > kListCap ||
+        L.lcap % 4 != 0 || L.scratch.vals == nullptr || L.scratch.meta == nullptr ||
+        (size_t)batches * L.lcap > L.scratch.cap_models)
+        return hipErrorInvalidValue;
+    const uint32_t pad0 = (p.cls[0].n + 63u) & ~63u, nchunks = ntot / 64;
+    const uint32_t off = list ? L.cap1 : 0u;
+    const uint32_t rows = std::min(L.lcap, list ? nslots : L.cap1);      // entries the list can hold, up to the cap
+    ScoreOut o{out.n0 + off, out.n1 + off, out.v0 + off, out.v1 + off, out.tot + off};
+    const ListArgs la{L.map + off, list ? L.count2 : L.count1, L.lcap, L.lstride, nslots};
+    DevProblem q = p;
+    q.lo = L.scratch;                                         // the buffer set's own scratch; no psum, no arrival counters
+    q.lo.psum = nullptr;
+    q.lo.arrive = nullptr;
+    constexpr uint32_t wpw = kLrThreads / 64;
+    constexpr bool kStride = GCR_LIST_ROWS > 0 || GCR_LIST_CPW > 1;
+    const uint32_t gx = (nchunks + wpw * GCR_LIST_CPW - 1) / (wpw * GCR_LIST_CPW);
+    const dim3 rgrid(gx, GCR_LIST_ROWS > 0 ? std::min<uint32_t>(rows, GCR_LIST_ROWS) : rows, batches);
+    const dim3 fgrid(rows, batches);
+    auto go = [&](auto ktag) {
+        constexpr int KIND = decltype(ktag)::value;
+        hipLaunchKernelGGL((k_list_resid<KIND, kStride>), rgrid, dim3(kLrThreads), 0, stream, q, models, T[0], T[1],
+                           pad0, nchunks, flag_band(T), la);
+        hipLaunchKernelGGL((k_list_fold<KIND>), fgrid, dim3(kLoThreads), 0, stream, q, pad0, nchunks, o, la);
+    };
+    switch (p.kind) {
+        case GCR_SOLVER_SCALE3: go(std::integral_constant<int, 0>{}); break;
+        case GCR_SOLVER_SCALE3_ORIGINAL: go(std::integral_constant<int, 1>{}); break;
+        default: go(std::integral_constant<int, 2>{}); break;
+    }
+    return hipGetLastError();
+}
+
 hipError_t launch_bound_contenders(int solver, const ScoreOut& sc, uint32_t nslots, uint32_t batches,
                                    const uint32_t m[2], const double Tm[2], const BoundLists& L, hipStream_t stream) {
     if (batches == 0 || nslots == 0) return hipSuccess;
     hipLaunchKernelGGL(k_bound_contenders, dim3(batches), dim3(kSelectThreads), 0, stream, solver, sc, L.ub0, L.ub1,
-                       L.state, nslots, m[0], m[1], Tm[0], Tm[1], L.cap1, L.lstride, L.map, L.count1, L.count2);
+                       L.state, nslots, m[0], m[1], Tm[0], Tm[1], L.cap1, L.lstride, L.map, L.count1, L.count2, L.lcap,
+                       L.over2);
     return hipGetLastError();
 }
 
