@@ -1860,6 +1860,20 @@ struct RectTraits {
         const int v = e ? atoi(e) : (int)kListCap;
         return (uint32_t)std::min(std::max(v, 0), (int)kListCap) & ~3u;
     }
+    // GCR_VERIFY_BOUND_OVER=split (read per call): the entries of a list past
+    // the list scorer's cap go to the batch scorer in a launch of their own, as
+    // before k_list_fold scored them itself (A/B; the records are the same)
+    static bool bound_over_on() {
+        const char* e = getenv("GCR_VERIFY_BOUND_OVER");
+        return !(e && e[0] == 's');
+    }
+    // GCR_VERIFY_BOUND_FSPLIT=0 (read per call): a wave of k_bound walks every
+    // feature for its own 16 entries, instead of a workgroup's waves sharing
+    // the features of one entry group (A/B; the bounds are the same)
+    static bool bound_fsplit_on() {
+        const char* e = getenv("GCR_VERIFY_BOUND_FSPLIT");
+        return !(e && e[0] == '0');
+    }
     static BoundLists bound_lists(gcr_problem* P, int set, uint32_t n, uint32_t gmax, uint32_t seeds, uint32_t lcap,
                                   ScoreOut& sc) {
         Workspace::BoundSet& b = P->w->vbnd[set];
@@ -1876,6 +1890,8 @@ struct RectTraits {
         L.live = b.live.p; L.nlive = b.cnt.p + 2 * (size_t)gmax;
         L.over1 = L.nlive + 1; L.over2 = L.over1 + gmax;
         L.lcap = lcap;
+        L.over = bound_over_on();
+        L.fsplit = bound_fsplit_on();
         if (lcap > 0) {
             const size_t pairs = small_score_pairs(P->dp), nm = (size_t)gmax * kListCap;
             b.lvals.ensure(nm * pairs); b.lmeta.ensure(nm * (pairs / 64));
@@ -1893,8 +1909,9 @@ struct RectTraits {
     // One launch group of `count` batches from slot s0 on stream s: generate,
     // live list, bound, seeds, their exact scores, contenders, theirs,
     // selection -- all queued, the list sizes stay on the device.  A list's
-    // scores: launch_list_scores and, where the list can be longer than L.lcap,
-    // launch_score_lists for the entries past it.  `all`: the
+    // scores: launch_list_scores, whose fold also scores the entries past
+    // L.lcap; without the list scorer (L.lcap == 0) launch_score_lists scores
+    // the whole list, with !L.over the entries past L.lcap.  `all`: the
     // live list holds every slot with a model.  rec[0 .. count): the records.
     static hipError_t bound_group(gcr_problem* P, const double Tm[2], uint64_t seed, uint64_t s0, uint32_t n,
                                   const uint32_t m[2], uint32_t count, int set, const BoundLists& L,
@@ -1907,9 +1924,9 @@ struct RectTraits {
         if (e == hipSuccess) e = launch_bound_seeds(P->solver, b.inc.p, b.models.p, n, count, m, L, s);
         for (int list = 0; list < 2; ++list) {
             if (list == 1 && e == hipSuccess) e = launch_bound_contenders(P->solver, sc, n, count, m, Tm, L, s);
-            // the first L.lcap entries by the list scorer, the rest by the batch scorer
             if (L.lcap > 0 && e == hipSuccess) e = launch_list_scores(P->dp, Tm, b.models.p, n, count, list, L, sc, s);
-            if (e == hipSuccess) e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, list, L, sc, s, L.lcap);
+            if ((L.lcap == 0 || !L.over) && e == hipSuccess)
+                e = launch_score_lists(P->dp, Tm, b.models.p, b.inc.p, n, count, list, L, sc, s, L.lcap);
         }
         if (e == hipSuccess) e = launch_bound_select(P->solver, sc, b.inc.p, b.models.p, n, s0, count, m, Tm, L, rec, s);
         return e;
@@ -2983,7 +3000,7 @@ public:
     // The bound path (bound.h; Tr::bound_group): launch groups of up to G
     // batches, clipped like the fused path's (fm_groups.h), go round s_, the
     // aux stream and the side stream, each with its own buffer set.  A group
-    // is a chain of dependent launches (eleven; eight when the batch scorer
+    // is a chain of dependent launches (ten; eight when the batch scorer
     // scores whole lists, Tr::bound_listcap), so one stream alone leaves the
     // GPU idle most of the time: the other streams' kernels fill it.
     // Every group ends with its own selection; evs[0..1] bracket the whole

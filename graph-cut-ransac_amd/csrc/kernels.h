@@ -309,6 +309,12 @@ struct BoundLists {
     uint32_t lcap = 0;              // 0: the batch scorer scores whole lists
     uint32_t* over1 = nullptr;
     uint32_t* over2 = nullptr;
+    // over: k_list_fold's workgroups score the entries past lcap themselves, no
+    // launch_score_lists for them (false: the batch scorer takes them, A/B)
+    bool over = true;
+    // fsplit: k_bound's waves share an entry group's features (false: a wave an
+    // entry group, every feature, A/B)
+    bool fsplit = true;
     SmallScratch scratch;           // the buffer set's: batches x lcap models (psum / arrive unused)
 };
 constexpr uint32_t kListCap = 128;  // list entries a batch the list scorer takes at most (a multiple of 4)
@@ -317,7 +323,8 @@ constexpr uint32_t kListCap = 128;  // list entries a batch the list scorer take
 // kDead for every other slot
 hipError_t launch_bound_live(int solver, bool all, const uint8_t* inc, const RectModel* models, uint32_t nh,
                              const BoundLists& L, hipStream_t stream);
-// k_bound<KIND>: ub0 / ub1 of the listed slots among the group's nh
+// k_bound<KIND, W>: ub0 / ub1 of the listed slots among the group's nh; W waves
+// share the features of 16 list entries (L.fsplit, else W = 1)
 hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel* models, uint32_t nh,
                         const BoundLists& L, hipStream_t stream);
 // the seeds: about L.seeds live slots a batch with the largest ub0 + ub1, in slot order
@@ -333,7 +340,9 @@ hipError_t launch_score_lists(const DevProblem& p, const double T[2], const Rect
 // the same sums, bit for bit, of the first min(count, L.lcap) entries of every
 // batch's list by the split scorer (k_list_resid + k_list_fold: one thread a
 // (model, feature) pair, then one workgroup a model folds its inlier values in
-// feature order); at most kSplitMaxPairs pairs, L.scratch for batches x lcap models
+// feature order); at most kSplitMaxPairs pairs, L.scratch for batches x lcap models.
+// With L.over the fold's workgroups also score the entries past lcap, each in
+// its own scratch row, so the whole list is scored by these two launches.
 hipError_t launch_list_scores(const DevProblem& p, const double T[2], const RectModel* models, uint32_t nslots,
                               uint32_t batches, int list, const BoundLists& L, const ScoreOut& out,
                               hipStream_t stream);

@@ -3549,13 +3549,80 @@ __global__ __launch_bounds__(kLrThreads) void k_list_resid(DevProblem p,
 }
 
 // k_lo_fold's work: grid (entries, batches), one workgroup an entry (a fixed
-// grid whose rows stride over the entries was measured slower, MEASUREMENTS.md §2)
+// grid whose rows stride over the entries was measured slower, MEASUREMENTS.md §2).
+// lmax > 0: the list holds up to lmax entries and the workgroup goes on with the
+// entries past the cap, e = j + cap, j + 2 cap, ... < count[b] (list_fold_over);
+// no further launch scores those entries (lmax == 0: they are k_score_split's,
+// launch_score_lists).
+//
+// lo_fold_model out of line for list_fold_over's loop: inlined in a loop, every
+// address and offset that follows from the thread index alone is hoisted out
+// of it and kept across it, which spills (99 VGPRs for kind 2); a call keeps
+// the fold's registers the fold's own.  Only p.lo is read by the fold.
 template <int KIND>
-__global__ __launch_bounds__(kLoThreads) void k_list_fold(DevProblem p, uint32_t pad0, uint32_t nchunks, ScoreOut out,
-                                                         ListArgs la) {
+__device__ __attribute__((noinline)) void list_fold_row(SmallScratch lo, uint32_t row, uint32_t pad0, uint32_t nchunks,
+                                                        ScoreOut out, uint32_t oi) {
+    DevProblem q{};
+    q.lo = lo;
+    lo_fold_model<KIND>(q, row, pad0, nchunks, out, oi);
+}
+// The entries e = e0, e0 + cap, ... < end of one workgroup of k_list_fold: its
+// 16 waves compute entry e's chunks (k_list_resid's work, wave w the chunks w,
+// w + 16, ...) into the workgroup's own scratch row, which is free once folded,
+// and fold that row into position obase + e of the list's scores.  The row is
+// this workgroup's alone, so a workgroup barrier orders an iteration's chunk
+// stores after the fold before them and before the fold that reads them; every
+// chunk's count word is rewritten in every iteration.  Out of line: the rare
+// path's registers stay out of the kernel's one fold (the arguments arrive in
+// vector registers; the workgroup-uniform words are made scalar again).
+template <int KIND>
+__device__ __attribute__((noinline)) void list_fold_over(DevProblem p, const typename ModelOf<KIND>::type* models,
+                                                         const uint32_t* hmap, double T0, double T1, uint32_t pad0,
+                                                         uint32_t nchunks, FlagBand fbm, ScoreOut out, uint32_t row,
+                                                         uint32_t e0, uint32_t end, uint32_t cap, uint32_t obase) {
+    __shared__ typename ModelOf<KIND>::type m_sh;
+    __shared__ ValueConst vc_sh;
+    auto uni = [](uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); };
+    pad0 = uni(pad0); nchunks = uni(nchunks); row = uni(row); e0 = uni(e0); end = uni(end); cap = uni(cap);
+    obase = uni(obase);
+    const int lane = threadIdx.x & 63;
+    const uint32_t wave = threadIdx.x >> 6;
+    const ListBits lb{{0.0, 0.0}, 0, 0.0, nullptr, nullptr};
+#pragma unroll 1
+    for (uint32_t e = e0; e < end; e += cap) {                // workgroup-uniform
+        __syncthreads();                                     // the fold before has read the row, the waves the model
+        if (threadIdx.x == 0) {
+            m_sh = models[hmap[e]];
+            vc_sh = value_const(m_sh, KIND == 1, KIND == 2);
+        }
+        __syncthreads();
+#pragma unroll 1
+        for (uint32_t c = wave; c < nchunks; c += kLoThreads / 64) {     // wave-uniform, no barrier inside
+            int cls;
+            uint32_t fi;
+            double x, y, f2, f3;
+            lo_pair_features<KIND>(p, c, lane, pad0, cls, fi, x, y, f2, f3);
+            lo_resid_chunk<KIND>(p, m_sh, vc_sh, nullptr, row, c, lane, T0, T1, pad0, nchunks, lb, fbm, fbm, x, y, f2,
+                                 f3, cls, fi);
+        }
+        __syncthreads();                                     // the row's chunks are stored: fold them
+        list_fold_row<KIND>(p.lo, row, pad0, nchunks, out, obase + e);
+    }
+}
+template <int KIND>
+__global__ __launch_bounds__(kLoThreads) void k_list_fold(DevProblem p,
+                                                         const typename ModelOf<KIND>::type* __restrict__ models,
+                                                         double T0, double T1, uint32_t pad0, uint32_t nchunks,
+                                                         FlagBand fbm, ScoreOut out, ListArgs la, uint32_t lmax) {
     const uint32_t b = blockIdx.y, j = blockIdx.x;
-    if (j >= min(la.count[b], la.cap)) return;                // whole workgroup, before any barrier
-    lo_fold_model<KIND>(p, b * la.cap + j, pad0, nchunks, out, b * la.lstride + j);
+    const uint32_t count = la.count[b];
+    if (j >= min(count, la.cap)) return;                      // whole workgroup, before any barrier
+    const uint32_t row = b * la.cap + j;
+    lo_fold_model<KIND>(p, row, pad0, nchunks, out, b * la.lstride + j);
+    const uint32_t end = min(count, lmax);
+    if (j + la.cap >= end) return;                            // workgroup-uniform: no entry of this row past the cap
+    list_fold_over<KIND>(p, models + (size_t)b * la.nslots, la.hmap + (size_t)b * la.lstride, T0, T1, pad0, nchunks, fbm,
+                         out, row, j + la.cap, end, la.cap, b * la.lstride);
 }
 
 // The approximate scores of k_lo_resid's models (blockIdx.x) from its chunk
@@ -4892,48 +4959,72 @@ __global__ __launch_bounds__(kLiveThreads) void k_bound_live(int solver, int all
     if (blockIdx.x == gridDim.x - 1 && t == 0) *count = base + tot;
 }
 
-// k_bound: a wave owns kBoundHW consecutive entries of the live list and walks
-// every feature, one feature a lane and round, with exactly the scorer's
+// k_bound: W waves share kBoundHW consecutive entries of the live list (W = 1:
+// a wave owns them and walks every feature), one feature a lane and round, with exactly the scorer's
 // constants (make_hyp, rpb_setup) and tests (rpb_scale, rpb_orient).  The
 // reject masks are compare ballots, so the counts are scalar bit counts;
 // nothing is queued or stored until the two counts of each slot at the end.
-// LDS holds the wave's constant records only.  The grid covers the list's
-// capacity nh; the waves past *count leave after the barrier.
+// LDS holds the entry groups' constant records and, with W > 1, the waves'
+// partial counts.  The grid covers the list's capacity nh; the waves past
+// *count walk nothing.
+//
+// W (GCR_BOUND_W: 1, 2 or 4): the waves that share one group of kBoundHW
+// entries.  The group's first wave builds its constants; wave s of the W walks
+// the feature rounds s, s + W, ... of each class (64 features a round) and
+// prefetches along its own share; the W partial counts of an entry are added in
+// LDS and the first wave stores the sums.  Integer sums: the counts do not
+// depend on W.  A live list a little longer than the SIMDs are many leaves
+// W = 1 with one or two long waves a SIMD and nothing to hide their latency;
+// W > 1 deals the same rounds out evenly (MEASUREMENTS.md §1).  W = 1 is the
+// A/B leg (GCR_VERIFY_BOUND_FSPLIT=0): a wave an entry group, every feature.
+#ifndef GCR_BOUND_W
+#define GCR_BOUND_W 4
+#endif
 constexpr int kBoundThreads = 256;
 constexpr int kBoundWaves = kBoundThreads / 64;
 constexpr int kBoundHW = 16;
+static_assert(GCR_BOUND_W == 1 || GCR_BOUND_W == 2 || GCR_BOUND_W == 4, "the waves of a workgroup in whole entry groups");
 
-template <int KIND>
+template <int KIND, int W>
 __global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double band0, double tan_tau1,
                                                          const RectModel* __restrict__ models,
                                                          const uint32_t* __restrict__ list,
                                                          const uint32_t* __restrict__ count, uint32_t nh,
                                                          uint32_t* __restrict__ ub0, uint32_t* __restrict__ ub1) {
     static_assert(KIND <= 2 && kBoundHW % 2 == 0 && kBoundHW <= 64, "rectification kinds, whole pairs");
-    __shared__ RPairBand pbs[kBoundWaves][kBoundHW / 2];
+    static_assert(kBoundWaves % W == 0, "whole entry groups a workgroup");
+    constexpr int kGroups = kBoundWaves / W;                  // entry groups a workgroup
+    __shared__ RPairBand pbs[kGroups][kBoundHW / 2];
+    __shared__ uint32_t part[W > 1 ? kBoundWaves : 1][2][kBoundHW];
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const uint32_t h0 = (blockIdx.x * kBoundWaves + (uint32_t)wave) * kBoundHW;
+    const int grp = wave / W;
+    const uint32_t share = (uint32_t)(wave % W);
+    const uint32_t h0 = (blockIdx.x * kGroups + (uint32_t)grp) * kBoundHW;
     const uint32_t nl = min(*count, nh);
     bool v = false;
     uint32_t hg = 0;
-    if (lane < kBoundHW) {
+    if (share == 0 && lane < kBoundHW) {
         v = h0 + lane < nl;
         hg = v ? list[h0 + lane] : 0u;
         v = v && hg < nh;
         const RectModel m = v ? models[hg] : default_model();
         const HypConst q = make_hyp<KIND>(m, band0);
-        rpb_setup(pbs[wave], lane, q, p.cls[0].amax, p.cls[1].amax, tan_tau1, KIND == 2, v);
+        rpb_setup(pbs[grp], lane, q, p.cls[0].amax, p.cls[1].amax, tan_tau1, KIND == 2, v);
     }
     __syncthreads();
-    if (h0 >= nl) return;
-    const RPairBand* pb = pbs[wave];
+    if constexpr (W == 1) {
+        if (h0 >= nl) return;
+    }
+    const bool work = h0 < nl;                                // wave-uniform; W > 1: every wave reaches the last barrier
+    constexpr uint32_t kStep = 64u * W;
+    const RPairBand* pb = pbs[grp];
     uint32_t cnt0[kBoundHW], cnt1[kBoundHW];
 #pragma unroll
     for (int q = 0; q < kBoundHW; ++q) cnt0[q] = cnt1[q] = 0;
     {
         const DevClass& c = p.cls[0];
-        const uint32_t n = c.n;
+        const uint32_t n = work ? c.n : 0u;
         // the next round's features are loaded before this round's tests
         double nx[3] = {0.0, 0.0, 0.0};
         auto load = [&](uint32_t base) {
@@ -4941,11 +5032,11 @@ __global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double ba
             const uint32_t ii = i < n ? i : 0u;      // out-of-range lanes read feature 0 and are masked
             nx[0] = c.x[ii]; nx[1] = c.y[ii]; nx[2] = c.a[ii];
         };
-        if (n > 0) load(0);
-        for (uint32_t base = 0; base < n; base += 64) {
+        if (share * 64u < n) load(share * 64u);
+        for (uint32_t base = share * 64u; base < n; base += kStep) {
             const bool ok = base + lane < n;
             const double f0 = nx[0], f1 = nx[1], f2 = nx[2];
-            if (base + 64 < n) load(base + 64);
+            if (base + kStep < n) load(base + kStep);
             const uint64_t okm = __builtin_amdgcn_ballot_w64(ok);
             const float pa = (float)f0, pb1 = (float)f1;
             const float pc = (f2 >= 0x1p-100 && f2 <= 0x1p100) ? (float)f2 : __builtin_nanf("");
@@ -4960,18 +5051,18 @@ __global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double ba
     }
     if constexpr (KIND == 2) {
         const DevClass& c = p.cls[1];
-        const uint32_t n = c.n;
+        const uint32_t n = work ? c.n : 0u;
         double nx[4] = {0.0, 0.0, 0.0, 0.0};
         auto load = [&](uint32_t base) {
             const uint32_t i = base + lane;
             const uint32_t ii = i < n ? i : 0u;
             nx[0] = c.x[ii]; nx[1] = c.y[ii]; nx[2] = c.c0[ii]; nx[3] = c.c1[ii];
         };
-        if (n > 0) load(0);
-        for (uint32_t base = 0; base < n; base += 64) {
+        if (share * 64u < n) load(share * 64u);
+        for (uint32_t base = share * 64u; base < n; base += kStep) {
             const bool ok = base + lane < n;
             const double f0 = nx[0], f1 = nx[1], f2 = nx[2], f3 = nx[3];
-            if (base + 64 < n) load(base + 64);
+            if (base + kStep < n) load(base + kStep);
             const uint64_t okm = __builtin_amdgcn_ballot_w64(ok);
             const float xf = (float)f0, yf = (float)f1;
             const float pb1 = (float)f2;                        // cos theta
@@ -4992,6 +5083,22 @@ __global__ __launch_bounds__(kBoundThreads) void k_bound(DevProblem p, double ba
         my0 = lane == q ? cnt0[q] : my0;
         my1 = lane == q ? cnt1[q] : my1;
     });
+    if constexpr (W > 1) {
+        // the group's W partial counts of each entry, added by its first wave
+        if (lane < kBoundHW) {
+            part[wave][0][lane] = my0;
+            part[wave][1][lane] = my1;
+        }
+        __syncthreads();
+        if (v) {
+            my0 = my1 = 0;
+#pragma unroll
+            for (int s = 0; s < W; ++s) {
+                my0 += part[wave + s][0][lane];
+                my1 += part[wave + s][1][lane];
+            }
+        }
+    }
     if (v) {
         ub0[hg] = my0;
         ub1[hg] = my1;
@@ -5681,12 +5788,19 @@ hipError_t launch_bound(const DevProblem& p, const double T[2], const RectModel*
     uint32_t* ub1 = L.ub1;
     double band0, tan_tau1;
     band_consts(T, band0, tan_tau1);
-    const dim3 grid((nh + kBoundWaves * kBoundHW - 1) / (kBoundWaves * kBoundHW)), block(kBoundThreads);
-    switch (p.kind) {
-        case GCR_SOLVER_SCALE3: hipLaunchKernelGGL(k_bound<0>, grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
-        case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL(k_bound<1>, grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
-        default: hipLaunchKernelGGL(k_bound<2>, grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
-    }
+    const dim3 block(kBoundThreads);
+    auto go = [&](auto wtag) {
+        constexpr int W = decltype(wtag)::value;
+        constexpr uint32_t per = kBoundWaves / W * kBoundHW;     // entries a workgroup
+        const dim3 grid((nh + per - 1) / per);
+        switch (p.kind) {
+            case GCR_SOLVER_SCALE3: hipLaunchKernelGGL((k_bound<0, W>), grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
+            case GCR_SOLVER_SCALE3_ORIGINAL: hipLaunchKernelGGL((k_bound<1, W>), grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
+            default: hipLaunchKernelGGL((k_bound<2, W>), grid, block, 0, stream, p, band0, tan_tau1, models, list, count, nh, ub0, ub1); break;
+        }
+    };
+    if (L.fsplit) go(std::integral_constant<int, GCR_BOUND_W>{});
+    else go(std::integral_constant<int, 1>{});
     return hipGetLastError();
 }
 
@@ -5759,11 +5873,14 @@ hipError_t launch_list_scores(const DevProblem& p, const double T[2], const Rect
     const uint32_t gx = (nchunks + wpw * GCR_LIST_CPW - 1) / (wpw * GCR_LIST_CPW);
     const dim3 rgrid(gx, GCR_LIST_ROWS > 0 ? std::min<uint32_t>(rows, GCR_LIST_ROWS) : rows, batches);
     const dim3 fgrid(rows, batches);
+    // L.over: the fold's workgroups score the entries past the cap themselves
+    const uint32_t lmax = L.over ? (list ? nslots : L.cap1) : 0u;
     auto go = [&](auto ktag) {
         constexpr int KIND = decltype(ktag)::value;
         hipLaunchKernelGGL((k_list_resid<KIND, kStride>), rgrid, dim3(kLrThreads), 0, stream, q, models, T[0], T[1],
                            pad0, nchunks, flag_band(T), la);
-        hipLaunchKernelGGL((k_list_fold<KIND>), fgrid, dim3(kLoThreads), 0, stream, q, pad0, nchunks, o, la);
+        hipLaunchKernelGGL((k_list_fold<KIND>), fgrid, dim3(kLoThreads), 0, stream, q, models, T[0], T[1], pad0,
+                           nchunks, flag_band(T), o, la, lmax);
     };
     switch (p.kind) {
         case GCR_SOLVER_SCALE3: go(std::integral_constant<int, 0>{}); break;
