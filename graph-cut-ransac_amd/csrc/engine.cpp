@@ -66,6 +66,7 @@
 #include "match_select.h"
 #include "match_knn.h"
 #include "match_sets.h"
+#include "verify_many.h"
 
 using namespace gcr;
 
@@ -555,6 +556,7 @@ struct gcr_ctx {
     std::mutex ws_mu;
     std::vector<std::unique_ptr<Workspace>> ws_free;
     MatchWorkspace match_ws;            // the descriptor sets' matching workspace (match_sets.h)
+    MatchWorkspace many_ws;             // gcr_verify_many's workspace: the same grow-only block and staging
 };
 
 // A communicator rank for the hypothesis-sharded run (RCCL, one process per
@@ -2156,7 +2158,7 @@ public:
         thr_[0] = P->thr0(prm);
         thr_[1] = prm.orientation_residual_thresh;
         for (int c = 0; c < 2; ++c) {
-            Tm_[c] = (2.25 * thr_[c]) * thr_[c];            // MSAC_scoring_function.hpp:64
+            Tm_[c] = msac_sq_threshold(thr_[c]);            // MSAC_scoring_function.hpp:64
             const double t = 1.5 * thr_[c];                 // GCRANSAC.h:207-208
             Tlo_[c] = t * t;
         }
@@ -5130,6 +5132,7 @@ void gcr_destroy(gcr_ctx* ctx) {
     if (ctx->pev1) (void)hipEventDestroy(ctx->pev1);
     if (ctx->pdone) (void)hipEventDestroy(ctx->pdone);
     match_workspace_free(ctx->match_ws);
+    match_workspace_free(ctx->many_ws);
     if (ctx->side) (void)hipStreamDestroy(ctx->side);
     if (ctx->aux) (void)hipStreamDestroy(ctx->aux);
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
@@ -5820,14 +5823,6 @@ int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, 
         y2[j] = r[3];
     }
     *count_out = 0;
-    if (solver == GCR_SOLVER_HOMOGRAPHY4) {
-        // kernels.hip attempt<3>
-        GeoModel g = default_geo();
-        if (!valid_sample_h4(x1, y1, x2, y2) || !solve_h4(x1, y1, x2, y2, g)) return GCR_OK;
-        for (int q = 0; q < 9; ++q) models_out[q] = g.h[q];
-        *count_out = 1;
-        return GCR_OK;
-    }
     if (solver == GCR_SOLVER_ESSENTIAL5) {
         // kernels.hip attempt_e: normalised rows, up to kEModels models
         GeoModel ms[kEModels];
@@ -5837,16 +5832,8 @@ int gcr_host_solve_minimal(int solver, const double* correspondences, size_t n, 
         *count_out = (uint32_t)cnt;
         return GCR_OK;
     }
-    // kernels.hip attempt_f and the winning lane's models
-    F7Basis b;
-    if (solve_f7_basis(x1, y1, x2, y2, b) == 0) return GCR_OK;
-    uint32_t k = 0;
-    for (int q = 0; q < 3; ++q)
-        if (b.valid & (1u << q)) {
-            f7_model(b, f7_root(b, q), models_out + 9 * k);
-            ++k;
-        }
-    *count_out = k;
+    // kernels.hip attempt<3>, or attempt_f and the winning lane's models (verify_many.h)
+    *count_out = host_solve_minimal_hf(solver, x1, y1, x2, y2, models_out);
     return GCR_OK;
 }
 
@@ -6231,8 +6218,9 @@ double gcr_host_math(int op, double a, double b) {
 int gcr_host_sample(uint64_t seed, uint64_t index, uint32_t sub, uint32_t stream, uint32_t cls, uint64_t n,
                     uint32_t m, uint32_t* out) {
     if (!out || m > 32) return set_err(GCR_EINVAL, "bad sample request");
-    WordStream ws(seed, index, sub, stream, cls);
-    return sample_distinct<32>(ws, n, (int)m, out) ? GCR_OK : set_err(GCR_EINTERNAL, "sample budget exhausted");
+    return host_sample_uniform(seed, index, sub, stream, cls, n, m, out)
+               ? GCR_OK
+               : set_err(GCR_EINTERNAL, "sample budget exhausted");
 }
 
 static int check_prosac_args(size_t n, uint32_t m, uint64_t convergence) {
@@ -6905,6 +6893,126 @@ int gcr_debug_match_workspace(gcr_ctx* ctx, uint64_t out[2]) {
     out[0] = ctx->match_ws.allocs;
     out[1] = ctx->match_ws.dev_bytes;
     return GCR_OK;
+}
+
+// ------------------------------------------------- many small problems ----
+}  // extern "C"
+
+namespace {
+// The checks of both verify_many entries (verify_many.h); the rows' values are
+// scanned over the host pool, the report is the first bad row in call order.
+int many_check(int solver, const double* rows, const uint64_t* row_offset, size_t nproblems, const double* thresholds,
+               const uint64_t* seeds, uint32_t nslots, const void* out) {
+    const std::string bad = many_check_shape(solver, rows, row_offset, nproblems, thresholds, seeds, nslots, out);
+    if (!bad.empty()) return set_err(GCR_EINVAL, "%s", bad.c_str());
+    const size_t parts = std::min<size_t>(nproblems, 64), step = (nproblems + parts - 1) / parts;
+    std::vector<std::pair<size_t, size_t>> first(parts, {SIZE_MAX, 0});
+    host_pool().parallel_for(parts, [&](size_t q) {
+        for (size_t p = q * step; p < std::min(nproblems, (q + 1) * step); ++p) {
+            const ptrdiff_t i = many_first_nonfinite(rows + 4 * row_offset[p], 4 * (row_offset[p + 1] - row_offset[p]));
+            if (i >= 0) {
+                first[q] = {p, (size_t)i / 4};
+                return;
+            }
+        }
+    });
+    for (const auto& f : first)
+        if (f.first != SIZE_MAX) return set_err(GCR_EINVAL, "%s", many_bad_row(f.first, f.second).c_str());
+    return GCR_OK;
+}
+
+// GCR_MANY_BLOCK (read per call; tests): the slots per workgroup of k_many,
+// 64, 128 or 256 (the default).  The result does not depend on it.
+uint32_t many_block() {
+    const char* e = getenv("GCR_MANY_BLOCK");
+    const int v = e ? atoi(e) : 0;
+    return (v == 64 || v == 128) ? (uint32_t)v : (uint32_t)kManyBlock;
+}
+
+size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
+}  // namespace
+
+extern "C" {
+
+int gcr_host_verify_many(int solver, const double* rows, const uint64_t* row_offset, size_t nproblems,
+                         const double* thresholds, const uint64_t* seeds, uint32_t nslots, int threads,
+                         gcr_many_result* out, uint8_t* masks_out) {
+    if (int e = many_check(solver, rows, row_offset, nproblems, thresholds, seeds, nslots, out)) return e;
+    return guard([&]() -> int {
+        host_verify_many(solver, rows, row_offset, nproblems, thresholds, seeds, nslots, threads, out, masks_out);
+        return GCR_OK;
+    });
+}
+
+int gcr_verify_many(gcr_ctx* ctx, int solver, const double* rows, const uint64_t* row_offset, size_t nproblems,
+                    const double* thresholds, const uint64_t* seeds, uint32_t nslots, gcr_many_result* out,
+                    uint8_t* masks_out, double* ms_kernel_out) {
+    if (int e = many_check(solver, rows, row_offset, nproblems, thresholds, seeds, nslots, out)) return e;
+    if (!ctx) return set_err(GCR_EINVAL, "verify_many: null context");
+    const uint32_t block = many_block();
+    const uint64_t nblk = (nslots + block - 1) / block;
+    if (nproblems >= (1ull << 31) || (uint64_t)nproblems * nblk > 0x7fffffffull)
+        return set_err(GCR_EINVAL, "verify_many: nproblems x slot blocks = %llu exceeds one launch's 2^31 - 1 workgroups",
+                       (unsigned long long)((uint64_t)nproblems * nblk));
+    return guard([&]() -> int {
+        HIPC(hipSetDevice(ctx->device));
+        MatchWorkspace& ws = ctx->many_ws;
+        std::lock_guard<std::mutex> lk(ws.mu);
+        hipStream_t s = ctx->stream;
+        const size_t total = (size_t)row_offset[nproblems], P = nproblems;
+        // device block: [columns | problems | offsets] (one upload), the
+        // partials, [records | masks] (one download); the staging mirrors the
+        // first and the last region
+        const size_t b_cols = up256(4 * total * sizeof(double)), b_probs = up256(P * sizeof(ManyProb)),
+                     b_offs = up256((P + 1) * sizeof(uint32_t)), b_up = b_cols + b_probs + b_offs,
+                     b_part = up256(P * (size_t)nblk * sizeof(ManyPartial)), b_res = up256(P * sizeof(gcr_many_result)),
+                     b_mask = masks_out ? up256(total) : 0, b_down = b_res + b_mask;
+        HIPC(match_workspace_grow(s, ws, b_up + b_part + b_down, b_up + b_down, false));
+        char* h_up = ws.pinned;
+        char* h_down = ws.pinned + b_up;
+        double* h_cols = reinterpret_cast<double*>(h_up);
+        ManyProb* h_probs = reinterpret_cast<ManyProb*>(h_up + b_cols);
+        uint32_t* h_offs = reinterpret_cast<uint32_t*>(h_up + b_cols + b_probs);
+        const size_t parts = std::min<size_t>(P, 64), step = (P + parts - 1) / parts;
+        host_pool().parallel_for(parts, [&](size_t q) {
+            for (size_t p = q * step; p < std::min(P, (q + 1) * step); ++p) {
+                const size_t o = (size_t)row_offset[p], n = (size_t)(row_offset[p + 1] - row_offset[p]);
+                const double* r = rows + 4 * o;
+                for (size_t i = 0; i < n; ++i)
+                    for (size_t k = 0; k < 4; ++k) h_cols[k * total + o + i] = r[4 * i + k];
+                h_probs[p] = ManyProb{seeds[p], msac_sq_threshold(thresholds[p]), (uint32_t)o, (uint32_t)n};
+                h_offs[p] = (uint32_t)o;
+            }
+        });
+        h_offs[P] = (uint32_t)total;
+        char* d_up = ws.dev;
+        ManyPartial* d_part = reinterpret_cast<ManyPartial*>(ws.dev + b_up);
+        char* d_down = ws.dev + b_up + b_part;
+        const bool timed = ms_kernel_out != nullptr;
+        if (timed)
+            for (int k = 0; k < 2; ++k)
+                if (!ws.ev[k]) HIPC(hipEventCreate(&ws.ev[k]));
+        HIPC(hipMemcpyAsync(d_up, h_up, b_up, hipMemcpyHostToDevice, s));
+        if (timed) HIPC(hipEventRecord(ws.ev[0], s));
+        hipError_t e = launch_verify_many(solver, reinterpret_cast<const double*>(d_up), (uint32_t)total,
+                                          reinterpret_cast<const ManyProb*>(d_up + b_cols),
+                                          reinterpret_cast<const uint32_t*>(d_up + b_cols + b_probs), (uint32_t)P,
+                                          nslots, block, d_part, reinterpret_cast<gcr_many_result*>(d_down),
+                                          masks_out ? reinterpret_cast<uint8_t*>(d_down + b_res) : nullptr, s);
+        if (e == hipSuccess && timed) e = hipEventRecord(ws.ev[1], s);
+        if (e == hipSuccess) e = hipMemcpyAsync(h_down, d_down, b_down, hipMemcpyDeviceToHost, s);
+        const hipError_t sy = hipStreamSynchronize(s);       // the one synchronisation; also after an error
+        HIPC(e);
+        HIPC(sy);
+        std::memcpy(out, h_down, P * sizeof(gcr_many_result));
+        if (masks_out) std::memcpy(masks_out, h_down + b_res, total);
+        if (timed) {
+            float ms = 0.f;
+            HIPC(hipEventElapsedTime(&ms, ws.ev[0], ws.ev[1]));
+            *ms_kernel_out = (double)ms;
+        }
+        return GCR_OK;
+    });
 }
 
 int gcr_host_grid_edges(const double* points, size_t n, int dims, const double* cell_size, uint64_t cell_number,

@@ -514,4 +514,27 @@ hipError_t launch_block_summary(int solver, const uint8_t* inc, const void* mode
 // streaming copy of `bytes` (a multiple of 16) for the HBM peak probe
 hipError_t launch_hbm_copy(const void* src, void* dst, size_t bytes, int nontemporal, hipStream_t stream);
 
+// Many small problems per call (verify_many.h is the definition).  The rows of
+// all problems lie packed in one SoA buffer: cols = four columns (x1, y1, x2,
+// y2) of total_rows doubles each; problem p owns rows off .. off + n - 1.
+struct ManyProb {
+    uint64_t seed;
+    double T;               // msac_sq_threshold(thr_p)
+    uint32_t off, n;
+};
+// one (problem, slot block)'s part: its best candidate and the block's sums
+struct ManyPartial {
+    double score;
+    uint32_t hyp, n0;       // hyp = slot * per + k, or kManyNone
+    uint64_t models, iterations;
+    double model[9];
+};
+constexpr int kManyBlock = 256;          // the largest slot block = workgroup of k_many
+// partial: nproblems * ceil(nslots / block) records; out: nproblems records;
+// mask: total_rows bytes or null.  block (64, 128 or 256) changes no result.
+// Three launches: k_many, k_many_merge and, with a mask, k_many_mask.
+hipError_t launch_verify_many(int solver, const double* cols, uint32_t total_rows, const ManyProb* probs,
+                              const uint32_t* offsets, uint32_t nproblems, uint32_t nslots, uint32_t block,
+                              ManyPartial* partial, gcr_many_result* out, uint8_t* mask, hipStream_t stream);
+
 }  // namespace gcr

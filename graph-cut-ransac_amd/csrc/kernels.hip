@@ -24,6 +24,7 @@
 #include "prosac_stop.h"
 #include "qr3.h"
 #include "sifth.h"
+#include "verify_many.h"
 
 #include <cmath>
 #include <cstdlib>
@@ -6695,6 +6696,300 @@ hipError_t launch_select_geo_batches(int solver, const ScoreOut& sc, const uint8
 
 hipError_t launch_compact(const uint8_t* inc, uint32_t n, uint32_t* map, uint32_t* count, hipStream_t stream) {
     hipLaunchKernelGGL(k_compact, dim3(1), dim3(kCompactThreads), 0, stream, inc, n, map, count);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------- many small problems ----
+// gcr_verify_many (verify_many.h is the definition): P small problems, S
+// slots each, in three launches.
+//
+// k_many: one workgroup per (problem, block of blockDim.x slots), one lane per
+// slot.  The lane generates its slot as G = 1 of k_generate / k_generate_f
+// (attempt<3> / attempt_f with uniform draws on a DevProblem whose class
+// points at the problem's rows in the packed columns), keeps the slot's 1 or
+// up to 3 models in registers and runs the literal sequential score loop over
+// the problem's rows.  Every lane reads the same row: the addresses are
+// wave-uniform, so the rows come through the scalar unit into SGPRs, as in
+// k_score, and cost the F instantiation no vector registers.  The lanes' best
+// candidates are merged with many_better (wave shuffles, then LDS across the
+// waves) into the block's ManyPartial, models and iterations are summed, and
+// the winning lane stores its model.
+// k_many_merge: one wave per problem merges its blocks' partials by the same
+// rule and writes the gcr_many_result.
+// k_many_mask: one lane per packed row; the row's problem by a search in the
+// offsets, then mask_rule 0 under the problem's merged best model.
+constexpr uint32_t kManyRows = 4;        // rows per group of k_many's score loop
+
+template <class V>
+__device__ __forceinline__ void many_merge_from(double& s, uint32_t& h, uint32_t& n0, V& tag, int d) {
+    const double so = __shfl_down(s, d);
+    const uint32_t ho = __shfl_down(h, d), no = __shfl_down(n0, d);
+    const V to = __shfl_down(tag, d);
+    if (many_better(s, h, so, ho)) {
+        s = so;
+        h = ho;
+        n0 = no;
+        tag = to;
+    }
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kManyBlock) void k_many(const double* __restrict__ cols, uint32_t total,
+                                                     const ManyProb* __restrict__ probs, uint32_t nslots,
+                                                     uint32_t nblk, ManyPartial* __restrict__ part) {
+    constexpr uint32_t kM = KIND == 4 ? 7 : 4;
+    constexpr int kPer = KIND == 4 ? kFModels : 1;
+    static_assert(KIND == 3 || KIND == 4, "homography or fundamental matrix");
+    static_assert(kFModels == 3, "three model registers per lane");
+    const uint32_t p = blockIdx.x / nblk, blk = blockIdx.x % nblk;
+    const ManyProb pr = probs[p];
+    DevProblem dp{};
+    dp.kind = KIND;
+    dp.cls[0].x = cols + pr.off;
+    dp.cls[0].y = cols + (size_t)total + pr.off;
+    dp.cls[0].a = cols + 2 * (size_t)total + pr.off;
+    dp.cls[0].c0 = cols + 3 * (size_t)total + pr.off;
+    dp.cls[0].n = pr.n;
+    const DevClass& c = dp.cls[0];
+    const uint32_t s = blk * blockDim.x + threadIdx.x;
+    const bool have = s < nslots;
+
+    // generation, G = 1: attempts 0 .. 100 in order, the first with a model
+    GeoModel mk[kPer];
+    uint32_t cnt = 0, inc = have ? 102u : 0u;
+    if constexpr (KIND == 3) {
+        mk[0] = default_geo();
+        if (have)
+            for (uint32_t a = 0; a < 101; ++a) {
+                GeoModel m = default_geo();
+                if (attempt<3>(dp, pr.seed, s, a, m, UniformDraw{})) {
+                    mk[0] = m;
+                    cnt = 1;
+                    inc = a + 1;
+                    break;
+                }
+            }
+    } else {
+        F7Basis b;
+        bool ok = false;
+        if (have)
+            for (uint32_t a = 0; a < 101; ++a)
+                if (attempt_f(dp, pr.seed, s, a, b, UniformDraw{}) > 0) {
+                    ok = true;
+                    inc = a + 1;
+                    break;
+                }
+#pragma unroll
+        for (int t = 0; t < kPer; ++t) mk[t] = default_geo();
+        if (ok) {
+            // k_generate_f's compaction of the valid roots, with constant
+            // register indices: the q-th root's model goes to position cnt
+#pragma unroll
+            for (int q = 0; q < 3; ++q)
+                if (b.valid & (1u << q)) {
+                    double fm[9];
+                    f7_model(b, f7_root(b, q), fm);
+#pragma unroll
+                    for (int t = 0; t < kPer; ++t)
+                        if ((uint32_t)t == cnt)
+                            for (int j = 0; j < 9; ++j) mk[t].h[j] = fm[j];
+                    ++cnt;
+                }
+        }
+    }
+
+    // score: k_score's sequential loop, the rows at wave-uniform addresses
+    uint32_t n0[kPer];
+    double v0[kPer];
+#pragma unroll
+    for (int t = 0; t < kPer; ++t) {
+        n0[t] = 0;
+        v0[t] = 0.0;
+    }
+    const double T = pr.T;
+    // rows in groups of kManyRows: a group's scalar loads are issued together
+    // and waited for once, so one load latency is spread over the group's
+    // arithmetic; the rows are still folded one after the other, in order
+    auto score_row = [&](double x1, double y1, double x2, double y2) {
+#pragma unroll
+        for (int t = 0; t < kPer; ++t) {
+            const double r2 = geo_sq_residual<KIND>(x1, y1, x2, y2, mk[t].h);
+            if (r2 <= T) {
+                n0[t] += 1;
+                v0[t] += -r2;
+            }
+        }
+    };
+    uint32_t i = 0;
+    for (; i + kManyRows <= c.n; i += kManyRows) {
+        double rx[kManyRows], ry[kManyRows], ra[kManyRows], rc[kManyRows];
+#pragma unroll
+        for (uint32_t u = 0; u < kManyRows; ++u) {
+            rx[u] = c.x[i + u];
+            ry[u] = c.y[i + u];
+            ra[u] = c.a[i + u];
+            rc[u] = c.c0[i + u];
+        }
+#pragma unroll
+        for (uint32_t u = 0; u < kManyRows; ++u) score_row(rx[u], ry[u], ra[u], rc[u]);
+    }
+    for (; i < c.n; ++i) score_row(c.x[i], c.y[i], c.a[i], c.c0[i]);
+
+    // the lane's best, then the block's
+    double bs = 0.0;
+    uint32_t bh = kManyNone, bn = 0;
+#pragma unroll
+    for (int t = 0; t < kPer; ++t)
+        if ((uint32_t)t < cnt) {
+            const double sum = many_finish_score(n0[t], v0[t], kM, T);
+            if (bs < sum) {
+                bs = sum;
+                bh = s * (uint32_t)kPer + (uint32_t)t;
+                bn = n0[t];
+            }
+        }
+    uint32_t nm = cnt, its = inc, tag = 0;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        many_merge_from(bs, bh, bn, tag, d);
+        nm += __shfl_down(nm, d);
+        its += __shfl_down(its, d);
+    }
+    constexpr int kWaves = kManyBlock / 64;
+    __shared__ double s_s[kWaves];
+    __shared__ uint32_t s_h[kWaves], s_n[kWaves], s_nm[kWaves], s_its[kWaves], s_win;
+    const uint32_t w = threadIdx.x >> 6, nw = (blockDim.x + 63u) >> 6;
+    if ((threadIdx.x & 63u) == 0) {
+        s_s[w] = bs;
+        s_h[w] = bh;
+        s_n[w] = bn;
+        s_nm[w] = nm;
+        s_its[w] = its;
+    }
+    __syncthreads();
+    ManyPartial* out = part + blockIdx.x;
+    if (threadIdx.x == 0) {
+        for (uint32_t v = 1; v < nw; ++v) {
+            if (many_better(bs, bh, s_s[v], s_h[v])) {
+                bs = s_s[v];
+                bh = s_h[v];
+                bn = s_n[v];
+            }
+            nm += s_nm[v];
+            its += s_its[v];
+        }
+        out->score = bs;
+        out->hyp = bh;
+        out->n0 = bn;
+        out->models = nm;
+        out->iterations = its;
+        if (bh == kManyNone) {
+            const GeoModel def = default_geo();
+            for (int j = 0; j < 9; ++j) out->model[j] = def.h[j];
+        }
+        s_win = bh;
+    }
+    __syncthreads();
+    const uint32_t win = s_win;
+    if (win != kManyNone && have && win / (uint32_t)kPer == s) {
+        const uint32_t k = win % (uint32_t)kPer;
+#pragma unroll
+        for (int t = 0; t < kPer; ++t)
+            if ((uint32_t)t == k)
+                for (int j = 0; j < 9; ++j) out->model[j] = mk[t].h[j];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_many_merge(const ManyPartial* __restrict__ part, uint32_t nblk,
+                                                    uint32_t nproblems, uint32_t per,
+                                                    gcr_many_result* __restrict__ out) {
+    const uint32_t p = blockIdx.x * 4u + (threadIdx.x >> 6), lane = threadIdx.x & 63u;
+    if (p >= nproblems) return;                 // whole waves leave; the kernel has no barrier
+    const ManyPartial* mine = part + (size_t)p * nblk;
+    double bs = 0.0;
+    uint32_t bh = kManyNone, bn = 0, bj = 0;
+    unsigned long long nm = 0, its = 0;
+    for (uint32_t j = lane; j < nblk; j += 64) {
+        const ManyPartial& q = mine[j];
+        if (many_better(bs, bh, q.score, q.hyp)) {
+            bs = q.score;
+            bh = q.hyp;
+            bn = q.n0;
+            bj = j;
+        }
+        nm += q.models;
+        its += q.iterations;
+    }
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        many_merge_from(bs, bh, bn, bj, d);
+        nm += __shfl_down(nm, d);
+        its += __shfl_down(its, d);
+    }
+    if (lane != 0) return;
+    gcr_many_result r;
+    r.models = nm;
+    r.iterations = its;
+    r.best_slot = -1;
+    r.best_hypothesis = 0;
+    r.best_inliers = 0;
+    r.best_score = 0.0;
+    if (bh != kManyNone) {
+        r.best_slot = (int64_t)(bh / per);
+        r.best_hypothesis = bh % per;
+        r.best_inliers = bn;
+        r.best_score = bs;
+    }
+    for (int j = 0; j < 9; ++j) r.best_model[j] = mine[bj].model[j];   // a block without a best holds the default
+    out[p] = r;
+}
+
+template <int KIND>
+__global__ __launch_bounds__(kMaskBlock) void k_many_mask(const double* __restrict__ cols, uint32_t total,
+                                                          const ManyProb* __restrict__ probs,
+                                                          const uint32_t* __restrict__ offsets, uint32_t nproblems,
+                                                          const gcr_many_result* __restrict__ res,
+                                                          uint8_t* __restrict__ mask) {
+    const uint32_t i = blockIdx.x * (uint32_t)kMaskBlock + threadIdx.x;
+    if (i >= total) return;
+    uint32_t lo = 0, hi = nproblems;            // offsets[lo] <= i < offsets[hi]
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (offsets[mid] <= i) lo = mid;
+        else hi = mid;
+    }
+    const gcr_many_result& r = res[lo];
+    bool in = false;
+    if (r.best_slot >= 0) {
+        const double r2 = geo_sq_residual<KIND>(cols[i], cols[(size_t)total + i], cols[2 * (size_t)total + i],
+                                                cols[3 * (size_t)total + i], r.best_model);
+        in = mask_rule(r2, 0, probs[lo].T, 0.0);
+    }
+    mask[i] = in ? 1 : 0;
+}
+
+hipError_t launch_verify_many(int solver, const double* cols, uint32_t total_rows, const ManyProb* probs,
+                              const uint32_t* offsets, uint32_t nproblems, uint32_t nslots, uint32_t block,
+                              ManyPartial* partial, gcr_many_result* out, uint8_t* mask, hipStream_t stream) {
+    if (solver != GCR_SOLVER_HOMOGRAPHY4 && solver != GCR_SOLVER_FUNDAMENTAL7) return hipErrorInvalidValue;
+    if (block != 64 && block != 128 && block != (uint32_t)kManyBlock) return hipErrorInvalidValue;
+    if (nproblems == 0 || nslots == 0 || total_rows == 0) return hipErrorInvalidValue;
+    const uint32_t nblk = (nslots + block - 1) / block;
+    if ((uint64_t)nproblems * nblk > 0x7fffffffull) return hipErrorInvalidValue;
+    const dim3 grid(nproblems * nblk), mgrid((nproblems + 3) / 4), kgrid(blocks_for(total_rows, kMaskBlock));
+    if (solver == GCR_SOLVER_FUNDAMENTAL7) {
+        hipLaunchKernelGGL(k_many<4>, grid, dim3(block), 0, stream, cols, total_rows, probs, nslots, nblk, partial);
+        hipLaunchKernelGGL(k_many_merge, mgrid, dim3(256), 0, stream, partial, nblk, nproblems, (uint32_t)kFModels, out);
+        if (mask)
+            hipLaunchKernelGGL(k_many_mask<4>, kgrid, dim3(kMaskBlock), 0, stream, cols, total_rows, probs, offsets,
+                               nproblems, out, mask);
+    } else {
+        hipLaunchKernelGGL(k_many<3>, grid, dim3(block), 0, stream, cols, total_rows, probs, nslots, nblk, partial);
+        hipLaunchKernelGGL(k_many_merge, mgrid, dim3(256), 0, stream, partial, nblk, nproblems, 1u, out);
+        if (mask)
+            hipLaunchKernelGGL(k_many_mask<3>, kgrid, dim3(kMaskBlock), 0, stream, cols, total_rows, probs, offsets,
+                               nproblems, out, mask);
+    }
     return hipGetLastError();
 }
 

@@ -134,6 +134,22 @@ class MatchOptions(C.Structure):
     ]
 
 
+class ManyResult(C.Structure):
+    """gcr_many_result: one problem's record of gcr_verify_many"""
+    _fields_ = [
+        ("models", C.c_uint64),
+        ("iterations", C.c_uint64),
+        ("best_slot", C.c_int64),
+        ("best_hypothesis", C.c_uint32),
+        ("best_inliers", C.c_uint32),
+        ("best_score", C.c_double),
+        ("best_model", C.c_double * 9),
+    ]
+
+
+MANY_DT = np.dtype(ManyResult)
+
+
 # int (*)(void* user, const void* send, void* recv, size_t bytes)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t)
 
@@ -300,6 +316,11 @@ def _load():
     L.gcr_knn_descriptors.argtypes = [vp, vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, vp, vp, dp]
     L.gcr_host_knn_descriptors.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_uint32, C.c_uint32, C.c_int, vp, vp]
     L.gcr_knn_sets.argtypes = [vp, vp, vp, C.c_uint32, vp, vp, dp]
+    # many small problems per call (csrc/verify_many.h): packed rows, offsets (uint64), thresholds, seeds in;
+    # gcr_many_result records and the packed masks out
+    mrp = C.POINTER(ManyResult)
+    L.gcr_verify_many.argtypes = [vp, C.c_int, vp, vp, C.c_size_t, vp, vp, C.c_uint32, mrp, vp, dp]
+    L.gcr_host_verify_many.argtypes = [C.c_int, vp, vp, C.c_size_t, vp, vp, C.c_uint32, C.c_int, mrp, vp]
     L.gcr_host_grid_edges.argtypes = [dp, C.c_size_t, C.c_int, dp, C.c_uint64, u32p, C.c_size_t,
                                       C.POINTER(C.c_size_t)]
     L.gcr_host_bk_energy.argtypes = [C.c_size_t, dp, u32p, dp, C.c_size_t, u8p]

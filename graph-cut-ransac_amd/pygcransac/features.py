@@ -33,7 +33,7 @@ import numpy as np
 __all__ = ["scale_features_from_sift", "orientation_features_from_sift", "keypoints_to_array", "perspective_warp",
            "warp_geometry", "BORDER_CONSTANT", "BORDER_REPLICATE", "match_descriptors", "quantize_descriptors",
            "correspondences_from_matches", "match_descriptors_guided", "fundamental_from_essential", "DescriptorSet",
-           "match_pairs", "knn_descriptors", "matches_from_knn"]
+           "match_pairs", "knn_descriptors", "matches_from_knn", "verify_pairs"]
 
 # OpenCV's border codes (cv2.BORDER_CONSTANT = 0, cv2.BORDER_REPLICATE = 1)
 BORDER_CONSTANT, BORDER_REPLICATE = 0, 1
@@ -507,6 +507,7 @@ class DescriptorSet:
         import ctypes as C
 
         self._n, self._dim, self._has_kp = int(d.shape[0]), int(d.shape[1]), p is not None
+        self._positions = p                               # the host copy (verify_pairs builds its rows from it)
         self._ctx = N.context(device)                     # the context outlives the set: kept for the process
         out = C.c_void_p()
         N.check(N.lib.gcr_descriptors_create(self._ctx, d.ctypes.data, self._n, self._dim,
@@ -680,6 +681,92 @@ def match_pairs(sets, pairs, ratio=0.8, mutual=True):
     for k in range(len(pr)):
         lo, m = int(offsets[k]), int(counts[k])
         out.append((matches[lo:lo + m].astype(np.int64), ratios[lo:lo + m].copy()))
+    return out
+
+
+def verify_pairs(sets, pairs, kind, threshold, ratio=0.8, mutual=True, iterations=1024, seed=0, refine=False, *,
+                 backend="gpu", device=None):
+    """Match many pairs of images and verify every pair's geometry, each step
+    one call: ``match_pairs(sets, pairs, ratio, mutual)``, then
+    ``correspondences_from_matches`` per pair, then
+    ``pygcransac.verify_many(rows, kind, threshold, iterations, seed=seed,
+    refine=refine)`` on the pairs that have enough matches.
+
+    ``sets`` is a sequence of ``DescriptorSet`` with keypoints, ``pairs`` a
+    sequence of index pairs into it.  ``kind`` is ``"homography"`` or
+    ``"fundamental"``; ``threshold`` and ``seed`` are a scalar or one value per
+    pair.  ``backend="host"`` runs both steps' host twins without a GPU and
+    gives the same bytes; ``sets`` are then ``(desc, keypoints)`` tuples, which
+    ``backend="gpu"`` accepts as well (it uploads them for the call).
+
+    Returns one ``(matches, ratios, record)`` per pair: ``match_pairs``'s
+    arrays and ``verify_many``'s dict.  A pair with fewer matches than a
+    minimal sample (4 / 7) is not sent down: its record has ``model=None``,
+    an all-False mask, zero inliers, score and iterations and slot -1.  A set
+    without keypoints is a ValueError."""
+    from . import pygcransac as G
+
+    if kind not in _GUIDED_KINDS:
+        raise ValueError(f"kind must be 'homography' or 'fundamental', got {kind!r}")
+    if backend not in ("gpu", "host"):
+        raise ValueError(f"backend must be 'gpu' or 'host', got {backend!r}")
+    sets = list(sets)
+    pr = np.asarray(pairs)
+    if pr.size == 0:
+        pr = np.zeros((0, 2), dtype=np.int64)
+    if pr.ndim != 2 or pr.shape[1] != 2 or not np.issubdtype(pr.dtype, np.integer):
+        raise ValueError("pairs must be a sequence of integer pairs (ia, ib)")
+    if pr.size and (pr.min() < 0 or pr.max() >= len(sets)):
+        raise ValueError(f"pairs index past the {len(sets)} sets")
+    tuples = [not isinstance(s, DescriptorSet) for s in sets]
+    pos = []
+    for k, s in enumerate(sets):
+        if tuples[k]:
+            if not (isinstance(s, (tuple, list)) and len(s) == 2):
+                raise ValueError(f"sets[{k}] must be a DescriptorSet or a (desc, keypoints) tuple")
+            if s[1] is None:
+                raise ValueError(f"sets[{k}] has no keypoints")
+            pos.append(_positions(s[1], f"sets[{k}] keypoints"))
+        else:
+            if backend == "host":
+                raise ValueError("backend='host' takes (desc, keypoints) tuples: a DescriptorSet lives on the GPU")
+            if not s.has_keypoints:
+                raise ValueError(f"sets[{k}] has no keypoints")
+            pos.append(s._positions)
+    if backend == "host":
+        found = [match_descriptors(sets[ia][0], sets[ib][0], ratio, mutual, backend="host") for ia, ib in pr.tolist()]
+    else:
+        made = [DescriptorSet(s[0], s[1], device=device) if tuples[k] else None for k, s in enumerate(sets)]
+        try:
+            found = match_pairs([m if m is not None else s for m, s in zip(made, sets)], pr, ratio, mutual)
+        finally:
+            for m in made:
+                if m is not None:
+                    m.close()
+    need = 4 if kind == "homography" else 7
+    rows = []
+    for (ia, ib), (matches, _) in zip(pr.tolist(), found):
+        a, b = pos[ia][matches[:, 0]], pos[ib][matches[:, 1]]
+        rows.append(np.ascontiguousarray(np.column_stack([a[:, 0], a[:, 1], b[:, 0], b[:, 1]])))
+    down = [k for k, r in enumerate(rows) if len(r) >= need]
+
+    def per_pair(v):
+        a = np.asarray(v)
+        return a if a.ndim == 0 else a[down] if a.shape == (len(rows),) else a
+
+    recs = G.verify_many([rows[k] for k in down], kind, per_pair(threshold), iterations, seed=per_pair(seed),
+                         backend=backend, device=device, refine=refine)
+    out = []
+    it = iter(recs)
+    for k, (matches, ratios) in enumerate(found):
+        if len(rows[k]) >= need:
+            rec = next(it)
+        else:
+            rec = {"model": None, "mask": np.zeros(len(rows[k]), dtype=bool), "inliers": 0, "score": 0.0, "slot": -1,
+                   "iterations": 0}
+            if refine:
+                rec["refined"] = None
+        out.append((matches, ratios, rec))
     return out
 
 

@@ -851,3 +851,100 @@ def findHomographySIFT(correspondences, h1, w1, h2, w2, probabilities=None, thre
                                 seed, device, batch_slots, return_stats, 4, neighborhood_size, guided_stop,
                                 min_weights=2, create=create, prosac_convergence=prosac_convergence,
                                 prosac_stop=prosac_stop, napsac_iterations=napsac_iterations)
+
+
+# ------------------------------------------------------ many small problems --
+_MANY_KINDS = {"homography": (N.SOLVER_HOMOGRAPHY4, 4), "fundamental": (N.SOLVER_FUNDAMENTAL7, 7)}
+
+
+def _per_problem(v, count, dtype, name):
+    a = np.asarray(v)
+    if a.ndim == 0:
+        a = np.full(count, a[()])
+    if a.shape != (count,):
+        raise ValueError(f"{name} must be a scalar or one value per problem ({count}), got shape {a.shape}")
+    if dtype is np.uint64:
+        if not np.issubdtype(a.dtype, np.integer) or (a.size and int(a.min()) < 0):
+            raise ValueError(f"{name} must be integers >= 0")
+    return np.ascontiguousarray(a, dtype=dtype)
+
+
+def verify_many(problems, kind, threshold, iterations=1024, *, seed=0, backend="gpu", device=None, refine=False):
+    """The best RANSAC hypothesis of many small correspondence problems in ONE
+    call (gcr_verify_many; csrc/verify_many.h is the definition): a fixed number
+    of launches for all problems, one upload, one synchronisation, one download.
+
+    ``problems`` is a sequence of (n_p, 4) float64 arrays of rows x1, y1, x2,
+    y2, each with at least 4 (``kind="homography"``) or 7
+    (``kind="fundamental"``) finite rows.  ``threshold`` (pixels, finite, > 0)
+    and ``seed`` are a scalar or one value per problem.  ``iterations`` is the
+    number of slots per problem, 1 .. 65536: every slot draws one uniform
+    minimal sample (retried up to 101 times until it yields a model), every
+    model is MSAC-scored against all of the problem's rows, and the first
+    strict best wins -- exactly what ``gcr_problem_verify_batch`` computes for
+    one resident problem.  No stop criterion, local optimisation or graph cut.
+
+    Returns a list with one dict per problem: ``model`` (3 x 3, the winning
+    hypothesis' own matrix, or ``None`` when no hypothesis scored above 0),
+    ``mask`` (bool, n_p: the model's MSAC inliers), ``inliers`` (= mask.sum()),
+    ``score``, ``slot`` (-1 without a model) and ``iterations`` (the sum of the
+    slots' iteration increments).  ``refine=True`` adds ``refined``: the
+    least-squares fit of the mask's rows (the estimators' non-minimal fit), or
+    ``None`` if it rejects them or there are fewer rows than it needs.
+    ``backend="host"`` runs the host twin without a GPU and returns the same
+    bytes."""
+    if kind not in _MANY_KINDS:
+        raise ValueError(f"kind must be 'homography' or 'fundamental', got {kind!r}")
+    if backend not in ("gpu", "host"):
+        raise ValueError(f"backend must be 'gpu' or 'host', got {backend!r}")
+    solver, m = _MANY_KINDS[kind]
+    probs = []
+    for k, q in enumerate(problems):
+        a = np.ascontiguousarray(q, dtype=np.float64)
+        if a.ndim != 2 or a.shape[1] != 4:
+            raise ValueError(f"problems[{k}] must have shape (n, 4): rows x1, y1, x2, y2; got {a.shape}")
+        probs.append(a)
+    P = len(probs)
+    if P == 0:
+        return []
+    thr = _per_problem(threshold, P, np.float64, "threshold")
+    seeds = _per_problem(seed, P, np.uint64, "seed")
+    S = _as_size_t(iterations, "iterations")
+    if not 1 <= S <= 65536:
+        raise ValueError(f"iterations must be in 1 .. 65536, got {S}")
+    off = np.zeros(P + 1, dtype=np.uint64)
+    off[1:] = np.cumsum([len(a) for a in probs])
+    rows = np.ascontiguousarray(np.concatenate(probs, axis=0))
+    total = int(off[-1])
+    out = (N.ManyResult * P)()
+    masks = np.zeros(max(total, 1), dtype=np.uint8)
+    if backend == "host":
+        N.check(N.lib.gcr_host_verify_many(solver, rows.ctypes.data, off.ctypes.data, P, thr.ctypes.data,
+                                           seeds.ctypes.data, S, 16, out, masks.ctypes.data))
+    else:
+        N.check(N.lib.gcr_verify_many(N.context(device), solver, rows.ctypes.data, off.ctypes.data, P,
+                                      thr.ctypes.data, seeds.ctypes.data, S, out, masks.ctypes.data, None))
+    rec = np.frombuffer(out, dtype=N.MANY_DT)
+    fit = N.lib.gcr_host_fit_h if solver == N.SOLVER_HOMOGRAPHY4 else N.lib.gcr_host_fit_f
+    res = []
+    for p in range(P):
+        r = rec[p]
+        lo, hi = int(off[p]), int(off[p + 1])
+        mask = masks[lo:hi].astype(bool)
+        have = int(r["best_slot"]) >= 0
+        d = {"model": r["best_model"].reshape(3, 3).copy() if have else None, "mask": mask,
+             "inliers": int(r["best_inliers"]), "score": float(r["best_score"]), "slot": int(r["best_slot"]),
+             "iterations": int(r["iterations"])}
+        if refine:
+            d["refined"] = None
+            idx = np.ascontiguousarray(np.flatnonzero(mask), dtype=np.uint32)
+            if have and len(idx) >= m:
+                M = np.zeros(9)
+                if N.check(fit(_dp(probs[p]), len(probs[p]), idx.ctypes.data_as(C.POINTER(C.c_uint32)), len(idx),
+                               _dp(M))) == 1:
+                    d["refined"] = M.reshape(3, 3)
+        res.append(d)
+    return res
+
+
+__all__.append("verify_many")

@@ -47,7 +47,8 @@ extern "C" {
  * correspondences (GCR_SOLVER_HOMOGRAPHY2_SIFT).  PROSAC sampling and its
  * stop (GCR_FLAG_PROSAC_STOP) likewise: a new flag bit and new functions.
  * NAPSAC sampling (gcr_problem_set_napsac and its host hooks): new functions
- * only. */
+ * only.  gcr_verify_many and its host twin: two new functions and their own
+ * result struct. */
 #define GCR_ABI_VERSION 5
 
 /* error codes */
@@ -454,6 +455,49 @@ int gcr_problem_verify_batch(gcr_problem* prob, const gcr_params* params, uint64
  * synchronisation per call.  Returns GCR_OK or an error code. */
 int gcr_problem_verify_batches(gcr_problem* prob, const gcr_params* params, uint64_t slot0, uint32_t nslots,
                                uint32_t nbatches, gcr_batch_result* out, gcr_stats* stats_out);
+
+/* ---- many small problems per call (csrc/verify_many.h is the definition) -- */
+/* The best hypothesis of `nproblems` independent small correspondence problems
+ * in one call: a fixed number of launches for all of them, one upload, one
+ * synchronisation, one download.  solver is GCR_SOLVER_HOMOGRAPHY4 or
+ * GCR_SOLVER_FUNDAMENTAL7, for the whole call.  rows holds every problem's
+ * N x 4 rows (x1, y1, x2, y2) back to back; problem p owns rows
+ * row_offset[p] .. row_offset[p + 1] - 1 (row_offset: nproblems + 1 ascending
+ * values, at least 4 / 7 rows per problem, fewer than 2^32 rows in all),
+ * thresholds[p] is its inlier threshold in pixels and seeds[p] its sampler
+ * seed.  out[p] is what gcr_problem_verify_batch(prob, params, 0, nslots)
+ * returns for a resident problem of those rows alone with uniform sampling,
+ * params.seed = seeds[p] and params.scale_residual_thresh = thresholds[p]:
+ * models, iterations, the best slot (-1: no hypothesis scored above 0) and its
+ * score and inlier count, plus the hypothesis inside the slot (0 for the
+ * homography, 0 .. 2 for the fundamental matrix) and its own nine doubles
+ * (gcr_debug_generate_h's, row-major; the default model 1 0 0 0 1 0 0 0 1
+ * without a best).  masks_out (may be NULL): row_offset[nproblems] bytes, row
+ * i's inlier decision under best_model by gcr_debug_mask_h's rule 0, all zero
+ * for a problem without a best; a problem's bytes sum to best_inliers.  The
+ * device result equals gcr_host_verify_many's byte for byte, for every
+ * GCR_MANY_BLOCK (64, 128 or 256 slots per workgroup; read per call, tests).
+ * GCR_EINVAL with a message naming the argument, before any GPU work (so also
+ * with a NULL context): a NULL array, another solver, nproblems == 0, offsets
+ * that do not start at 0 or descend, a problem with too few rows, 2^32 rows or
+ * more, a non-finite row, a threshold that is not finite and > 0, nslots
+ * outside 1 .. 65536.  ms_kernel_out may be NULL: HIP-event time of the
+ * kernels. */
+typedef struct gcr_many_result {
+    uint64_t models, iterations;
+    int64_t  best_slot;
+    uint32_t best_hypothesis, best_inliers;
+    double   best_score;
+    double   best_model[9];
+} gcr_many_result;
+int gcr_verify_many(gcr_ctx* ctx, int solver, const double* rows, const uint64_t* row_offset, size_t nproblems,
+                    const double* thresholds, const uint64_t* seeds, uint32_t nslots, gcr_many_result* out,
+                    uint8_t* masks_out, double* ms_kernel_out);
+/* host-only: the same by plain loops (no GPU); `threads` (clamped to 1..16)
+ * splits the problems only and does not change the result */
+int gcr_host_verify_many(int solver, const double* rows, const uint64_t* row_offset, size_t nproblems,
+                         const double* thresholds, const uint64_t* seeds, uint32_t nslots, int threads,
+                         gcr_many_result* out, uint8_t* masks_out);
 
 /* ---- parity / debug hooks (used by tests; GPU required unless noted) ---- */
 /* inc[i] in 1..101 (attempt of success) or 102 (no model), models[i] */
